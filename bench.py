@@ -1,6 +1,13 @@
 """MEPOL epoch benchmark on MI355X (BASELINE.json metric: epoch wall-clock + k-NN roofline).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C2S|C3|C4|C5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (epoch wall-clock
+and the k-NN roofline from the HIP events of the timed steps themselves).  --full adds the legs
+that take runs of their own: the live rocprofv3 --pmc passes for roofline.traffic, the
+iteration's MFMA kernels timed alone (roofline_iteration) and the CPU baseline.  --dump-outputs
+DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 Workloads (BASELINE.json configs):
   C3  (default) Ant-shaped batch: N = 400 x 500 = 200,000 particles, k-NN space d = 29, k = 30,
@@ -77,10 +84,18 @@ def parse(argv=None):
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: live rocprofv3 --pmc "
+                        "passes (roofline.traffic), the iteration's MFMA kernels timed alone "
+                        "(roofline_iteration) and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs (k-NN table, final "
+                        "entropy, loop counters, updated policy) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-sample-queries", type=int, default=16000)
     p.add_argument("--no-pmc", action="store_true",
-                   help="skip the live rocprofv3 --pmc passes for roofline.traffic (the stamped "
+                   help="with --full: skip the live rocprofv3 --pmc passes for roofline.traffic (the stamped "
                         "profiles/knn_pmc_<workload>.json is read instead)")
     p.add_argument("--selftest", action="store_true",
                    help="launcher plumbing only (no GPU): ranks rendezvous over gloo, time an "
@@ -313,6 +328,8 @@ def run(args):
             peers.append([synthetic_batch(cfg, s_, dev, r, shards)[0][:, 1:].reshape(-1, nf)
                           [:, :d].contiguous() for r in range(1, shards)])
     knn_events, roll_events, iters_done, entropies = [], [], [], []
+    last_step = args.warmup + args.steps - 1
+    kept = {}  # --dump-outputs: the last timed step's device outputs (references only)
 
     def one_epoch(i):
         T_ = T
@@ -357,7 +374,13 @@ def run(args):
                 opt, behavioral, target, last_valid, G, B, ns, cfg["eps"], cfg["kl_threshold"],
                 cfg["max_off_iters"], True, cfg["backtrack_coeff"], cfg["max_backtrack_try"],
                 cfg["lr"])
-        entropy, n_off, _, _ = res
+        entropy, n_off, bt_iter, lr_end = res
+        if args.dump_outputs and i == last_step:
+            kept.update(knn_distances=ep.D if sharded else D, knn_indices=ep.I if sharded else I,
+                        final_entropy=entropy, off_policy_iters=n_off, backtrack_iter=bt_iter,
+                        learning_rate=lr_end)
+            if rollout:
+                kept.update(rollout_states=st32, rollout_actions=ac32)
         behavioral.load_state_dict(last_valid.state_dict())
         target.load_state_dict(last_valid.state_dict())
         entropies.append(float(entropy))
@@ -391,6 +414,10 @@ def run(args):
         dist.all_gather(allk, kt)
         per_rank_knn = [float(x.item()) for x in allk]
     epoch_s = elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        # the epoch's result as its caller holds it: the behavioral policy after the epoch
+        kept.update({"policy." + n: v for n, v in behavioral.state_dict().items()})
+        dump_outputs(args.dump_outputs, kept)
 
     if rank != 0:
         if dist is not None:
@@ -498,7 +525,7 @@ def run(args):
         gbps = traffic / (knn_ms * 1e-3) / 1e9
         line["roofline"]["hbm_GBps"] = round(gbps, 1)
         line["roofline"]["hbm_frac"] = round(gbps / PEAK_HBM_GBPS, 4)
-    mlp = _mlp_roofline(it) if (it is not None and not sharded) else None
+    mlp = _mlp_roofline(it) if (args.full and it is not None and not sharded) else None
     if mlp:
         line["roofline_iteration"] = mlp
     if rollout:
@@ -508,11 +535,46 @@ def run(args):
         line["survey_reference_epoch_s"] = 9.10 if args.workload == "C2S" else None
     if rehearsal:
         line["config"]["rehearsal"] = f"{world} ranks on {torch.cuda.device_count()} GPU(s), gloo"
-    if not args.no_cpu_baseline and world == 1 and emul is None:
+    if args.full and not args.no_cpu_baseline and world == 1 and emul is None:
         line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample_queries, iters_done)
     _emit(line)
     if dist is not None:
         parallel.destroy_process_group(dist)
+
+
+DUMP_ARRAY_BYTES = 8 << 20    # per array; larger ones are row-sampled
+DUMP_TOTAL_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write {name: tensor | ndarray | scalar} as out_dir/<name>.npy, floating arrays in their
+    own precision (f32 / f64), everything else as f64 (k-NN indices are exact there).  An array
+    above DUMP_ARRAY_BYTES is cut to a fixed sample of its rows (sorted, drawn without
+    replacement from a generator seeded with `seed`, so two runs keep the same rows); the
+    whole dump stays under DUMP_TOTAL_BYTES.  Returns {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+    for name in sorted(arrays):
+        v = arrays[name]
+        if v is None:
+            continue
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v)
+        if a.ndim and a.nbytes > DUMP_ARRAY_BYTES:
+            row_bytes = a.nbytes // a.shape[0]
+            keep = np.sort(np.random.default_rng(seed).choice(
+                a.shape[0], size=max(1, DUMP_ARRAY_BYTES // row_bytes), replace=False))
+            a = a[keep]
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        total += a.nbytes
+        if total > DUMP_TOTAL_BYTES:
+            raise SystemExit(f"bench: --dump-outputs would exceed {DUMP_TOTAL_BYTES} bytes at "
+                             f"{name}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = a.shape
+    return written
 
 
 def knn_source_stamp():
@@ -752,7 +814,7 @@ def main(argv=None):
         return spawn(args, argv)
     cfg = WORKLOADS[args.workload]
     args.live_traffic = None
-    if (not args.no_pmc and not args.selftest and "WORLD_SIZE" not in os.environ
+    if (args.full and not args.no_pmc and not args.selftest and "WORLD_SIZE" not in os.environ
             and cfg.get("env") is None and not cfg.get("emulate_world")):
         if _under_profiler():
             args.live_traffic = (None, None, "bench runs under a profiler: live PMC passes skipped")

@@ -38,6 +38,47 @@ def test_bench_workloads_parse():
         assert args.workload == w and args.gpus == 2
 
 
+def test_bench_plain_and_full_options_parse():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.dump_outputs is None and plain.steps == 7
+    full = bench.parse(["--full", "--dump-outputs", "somewhere", "--no-pmc"])
+    assert full.full and full.dump_outputs == "somewhere" and full.no_pmc
+
+
+def test_dump_outputs_dtypes_sampling_and_size(tmp_path):
+    """--dump-outputs: f32 / f64 kept, anything else written as f64, an array above the
+    per-array budget cut to the same seeded rows on every call, the total under 64 MB."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rows = 3 * bench.DUMP_ARRAY_BYTES // (31 * 8) + 5      # ~3x the per-array budget
+    big = np.arange(rows * 31, dtype=np.float64).reshape(rows, 31)
+    arrays = {"big": torch.as_tensor(big), "idx": torch.arange(12).reshape(4, 3),
+              "w": torch.ones(5, dtype=torch.float32), "h": torch.tensor(-2.5, dtype=torch.float64),
+              "iters": 30, "absent": None}
+    a, b = tmp_path / "a", tmp_path / "b"
+    shapes = bench.dump_outputs(str(a), arrays)
+    bench.dump_outputs(str(b), arrays)
+    assert sorted(p.name for p in a.iterdir()) == ["big.npy", "h.npy", "idx.npy", "iters.npy",
+                                                   "w.npy"]
+    got = {p.stem: np.load(p) for p in a.iterdir()}
+    assert got["w"].dtype == np.float32 and got["big"].dtype == np.float64
+    assert got["idx"].dtype == np.float64 and np.array_equal(got["idx"].ravel(), np.arange(12))
+    assert got["h"].shape == () and got["h"] == -2.5 and got["iters"] == 30
+    n = bench.DUMP_ARRAY_BYTES // (31 * 8)
+    assert got["big"].shape == (n, 31) == shapes["big"]
+    first = (got["big"][:, 0] / 31).astype(np.int64)       # the rows kept: sorted, distinct
+    assert np.all(np.diff(first) > 0) and np.array_equal(got["big"], big[first])
+    assert np.array_equal(got["big"], np.load(b / "big.npy"))
+    assert sum(v.nbytes for v in got.values()) <= 64 * 10**6 == bench.DUMP_TOTAL_BYTES
+
+
 def test_emulated_dist_fills_peer_slots():
     """The R8 workloads run rank 0 of an 8-rank job on one GPU: every collective becomes local
     copies of the same size; gathers take registered peer tensors (the other shards' next states,

@@ -16,7 +16,7 @@ tail -1 "$out/smoke.log"
 echo "[final] k-NN counters"
 timeout -k 10 300 bash tools/knn_pmc.sh "$out/pmc" > "$out/pmc.log" 2>&1 || { tail -20 "$out/pmc.log"; exit 1; }
 echo "[final] bench (default)"
-timeout -k 10 400 python -u bench.py > "$out/bench_default.json" 2> "$out/bench_default.err" || { tail -20 "$out/bench_default.err"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err" || { tail -20 "$out/bench_default.err"; exit 1; }
 cat "$out/bench_default.json"
 echo "[final] bench under rocprofv3"
 root=$(pwd)

@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_gemm.py tests/test_gpu_poli
 tail -1 "$out/tests.log"
 for lib in main $v main $v; do
   L=$root/mepol_amd/libmepol_amd.so; [ $lib = main ] || L=$root/mepol_amd/libmepol_amd_$lib.so
-  MEPOL_AMD_LIB=$L timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 3 > "$out/bench_$lib.json" 2> "$out/bench_$lib.err" || { tail -20 "$out/bench_$lib.err"; exit 1; }
+  MEPOL_AMD_LIB=$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 3 > "$out/bench_$lib.json" 2> "$out/bench_$lib.err" || { tail -20 "$out/bench_$lib.err"; exit 1; }
   echo "$lib $(python3 -c "import json,sys; d=json.loads(open('$out/bench_$lib.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('knn_ms'), d.get('roofline_iteration', {}))")"
 done
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$root/$out/prof" -o run -- python3 "$root/bench.py" --no-cpu-baseline --steps 2 > "$root/$out/bench_prof.json" 2> "$root/$out/bench_prof.err" ) || { tail -20 "$out/bench_prof.err"; exit 1; }

@@ -9,5 +9,5 @@ tail -1 "$out/gpu_tests.log"
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" \
   > "$out/smoke.log" 2>&1 || { tail -20 "$out/smoke.log"; exit 1; }
 tail -1 "$out/smoke.log"
-timeout -k 10 400 python -u bench.py > "$out/bench_default.json" 2> "$out/bench_default.err" || { tail -20 "$out/bench_default.err"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err" || { tail -20 "$out/bench_default.err"; exit 1; }
 cat "$out/bench_default.json"

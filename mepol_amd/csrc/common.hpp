@@ -33,6 +33,17 @@ void set_error(const char* fmt, ...);
     }                                                                               \
   } while (0)
 
+// Raises Kernel's dynamic-LDS limit to `bytes` on its first call (one function-local static per
+// kernel: its initialisation is thread-safe) and returns that call's result ever after: a
+// failure is not retried, and the attribute is set only for the device that was current at
+// that first call (the library drives one device per process).
+template <auto Kernel>
+hipError_t max_dynamic_lds(int bytes) {
+  static const hipError_t rc = hipFuncSetAttribute(
+      (const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return rc;
+}
+
 // Error codes returned by the C ABI besides hipError_t values.
 enum : int {
   kErrBadArg = 1001,

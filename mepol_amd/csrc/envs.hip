@@ -614,13 +614,7 @@ static constexpr int kRollMwMaxH0 = 306;
 
 template <int ENV>
 static int rollout_mw_prepare() {
-  static bool attr = false;
-  if (!attr) {
-    MEPOL_HIP(hipFuncSetAttribute((const void*)rollout_mlp_mw_kernel<ENV>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kRollMwMaxH0 * 64 * (int)sizeof(double)));
-    attr = true;
-  }
+  MEPOL_HIP(max_dynamic_lds<rollout_mlp_mw_kernel<ENV>>(kRollMwMaxH0 * 64 * (int)sizeof(double)));
   return 0;
 }
 
@@ -756,12 +750,7 @@ extern "C" int mepol_rollout_mlp(int env_id, const double* W1, const double* b1,
   const size_t lds = (size_t)KL * threads * sizeof(double);
 #define MEPOL_ROLL(E, U)                                                                          \
   do {                                                                                            \
-    static bool attr = false;                                                                     \
-    if (!attr) {                                                                                  \
-      MEPOL_HIP(hipFuncSetAttribute((const void*)rollout_mlp_kernel<E, U>,                        \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));     \
-      attr = true;                                                                                \
-    }                                                                                             \
+    MEPOL_HIP((max_dynamic_lds<rollout_mlp_kernel<E, U>>(150 * 1024)));                           \
     hipLaunchKernelGGL((rollout_mlp_kernel<E, U>), g, dim3(threads), lds, st, W1, b1, h0, W2t, b2, \
                        h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T, states_rec,       \
                        actions_rec, visited, final_state, KL);                                    \

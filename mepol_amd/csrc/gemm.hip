@@ -14,7 +14,10 @@
 // one, and the swizzle puts each group's 16 reads on 16 distinct slots (the round-5 144-B
 // padded stride left two of them 2-way: SQ_LDS_BANK_CONFLICT 3.3e7 per C3 dh1 call); the
 // stores (8-lane groups, one row) stay conflict-free.
-#include "common.hpp"
+// d4, the fragment map and xcd_tile come from mfma_f64.hpp, the fixed-order sum of the dh1
+// kernel's row-block partials from reduce.hpp.
+#include "mfma_f64.hpp"
+#include "reduce.hpp"
 
 #include <type_traits>
 
@@ -31,15 +34,10 @@ constexpr int KP = 16;  // LDS row (doubles), swizzled by lds_slot
 __device__ __forceinline__ int lds_slot(int r, int c) {
   return c ^ (((r >> 1) & 1) | (((r >> 3) & 1) << 2));
 }
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-// XCD-aware tile order for a 1-D grid: workgroup L runs on XCD L % 8, so consecutive tiles
-// (the column tiles of one row block, which share the A rows) are given to consecutive
-// workgroups of the SAME XCD and meet in its L2.  A bijection on [0, ntiles).
-__device__ __forceinline__ int xcd_tile(int L, int ntiles) {
-  const int x = L & 7, s = L >> 3, q = ntiles >> 3, r = ntiles & 7;
-  return x * q + min(x, r) + s;
-}
+using mfma::d4;
+using mfma::frag_col;
+using mfma::frag_row;
+using mfma::xcd_tile;
 
 template <int WR, int WC, int FR, int FC>
 struct Cfg {
@@ -210,7 +208,6 @@ __global__ __launch_bounds__(WR * WC * 64) void gemm_nt_kernel(
   extern __shared__ double lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave / WC, wc = wave % WC;
-  const int fr = lane & 15, g = lane >> 4;
   const int ncb = (M + BN - 1) / BN;
   const int tile = xcd_tile(blockIdx.x, gridDim.x);
   const int64_t row0 = (int64_t)(tile / ncb) * BM;
@@ -218,17 +215,16 @@ __global__ __launch_bounds__(WR * WC * 64) void gemm_nt_kernel(
   d4 acc[FR][FC];
   gemm_mainloop<WR, WC, FR, FC>(A, N, K, lda, B, M, ldb, row0, col0, lds, acc);
 
-  // C/D map of the f64 16x16x4 MFMA: col = lane & 15, row = (lane >> 4) + 4 q.
 #pragma unroll
   for (int j = 0; j < FC; ++j) {
-    const int c = col0 + wc * FC * 16 + j * 16 + fr;
+    const int c = col0 + wc * FC * 16 + j * 16 + frag_col(lane);
     if (c >= M) continue;
     const double bc = bias ? bias[c] : 0.0;
 #pragma unroll
     for (int i = 0; i < FR; ++i)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int64_t r = row0 + wr * FR * 16 + i * 16 + g + 4 * q;
+        const int64_t r = row0 + wr * FR * 16 + i * 16 + frag_row(lane, q);
         if (r < N) {
           double v = acc[i][j][q] + bc;
           if (relu) v = fmax(v, 0.0);
@@ -243,11 +239,30 @@ __global__ __launch_bounds__(WR * WC * 64) void gemm_nt_kernel(
 // forward's h1) and reduces dz1^T [x | 1] over the tile's rows on the matrix cores, i.e. the
 // tile's contribution to dW1 (and db1 in column F).  The MFMA accumulator of dh1 already is
 // the A operand of that product (its k index = row); x comes from HBM as the B operand.
-// Row-block partials part[rb][c][F + 1] are summed in a fixed order by layer1_reduce_kernel.
+// Row-block partials part[rb][c][F + 1] are summed in a fixed order by sum_records.
 // Tiling: 8 waves x (32 rows x 80 cols), 256 x 80 tile: 5 column tiles for h0 = 400.
 namespace l1b {
 constexpr int WR = 8, WC = 1, FR = 2, FC = 5;
 using P = Cfg<WR, WC, FR, FC>;
+constexpr int kGroups = 16;  // sum_records' groups of row blocks
+
+inline int row_blocks(int64_t n) { return (int)((n + P::BM - 1) / P::BM); }
+inline size_t ws_bytes(int64_t n, int m, int F) {
+  return sum_records_bytes<kGroups>(row_blocks(n), (size_t)m * (F + 1));
+}
+
+// element e = c (F + 1) + f of the summed record: dW[c][f], db[c] in column F
+struct ScatterW1 {
+  int F;
+  double *dW, *db;
+  __device__ void operator()(int64_t e, double t) const {
+    const int c = (int)(e / (F + 1)), f = (int)(e % (F + 1));
+    if (f < F)
+      dW[(int64_t)c * F + f] = t;
+    else if (db)
+      db[c] = t;
+  }
+};
 }  // namespace l1b
 
 // MASK: relu'(h1) comes as the forward's bit mask (uint16 word kt of row r holds
@@ -374,56 +389,12 @@ __global__ __launch_bounds__(l1b::P::kThreads) void dh1_layer1_bwd_kernel(
   }
 }
 
-// dW[c][f] = sum_b part[b][c][f], db[c] = sum_b part[b][c][F] in two fixed-order stages: stage 1
-// sums row-block group g (kGroups of them, strided rows) for 64 elements per block; stage 2 sums
-// the groups in order.  (One block column per 64 elements with all row blocks serial was
-// latency-bound at 79 us for 782 x 12000 partials.)
-constexpr int kGroups = 16;
-
-__global__ __launch_bounds__(256) void layer1_reduce_kernel(const double* __restrict__ part,
-                                                            int nb, int M, int F,
-                                                            double* __restrict__ grp) {
-  __shared__ double sh[4][64];
-  const int64_t m = (int64_t)M * (F + 1);
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t e = (int64_t)blockIdx.x * 64 + l;
-  const int gi = blockIdx.y;
-  double s = 0.0;
-  if (e < m)
-    for (int b = gi + kGroups * w; b < nb; b += 4 * kGroups) s += part[(int64_t)b * m + e];
-  sh[w][l] = s;
-  __syncthreads();
-  if (w == 0 && e < m) grp[(int64_t)gi * m + e] = sh[0][l] + sh[1][l] + sh[2][l] + sh[3][l];
-}
-
-__global__ __launch_bounds__(256) void layer1_reduce2_kernel(const double* __restrict__ grp,
-                                                             int M, int F,
-                                                             double* __restrict__ dW,
-                                                             double* __restrict__ db) {
-  const int64_t m = (int64_t)M * (F + 1);
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= m) return;
-  double t = 0.0;
-#pragma unroll
-  for (int g = 0; g < kGroups; ++g) t += grp[(int64_t)g * m + e];
-  const int c = (int)(e / (F + 1)), f = (int)(e % (F + 1));
-  if (f < F)
-    dW[(int64_t)c * F + f] = t;
-  else if (db)
-    db[c] = t;
-}
-
 template <int WR, int WC, int FR, int FC>
 int launch_nt(const double* A, int64_t n, int k, int64_t lda, const double* B, int m,
               int64_t ldb, const double* bias, int relu, double* C, int64_t ldc,
               hipStream_t st) {
   using P = Cfg<WR, WC, FR, FC>;
-  static bool attr = false;
-  if (!attr) {
-    MEPOL_HIP(hipFuncSetAttribute((const void*)gemm_nt_kernel<WR, WC, FR, FC>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::kLds));
-    attr = true;
-  }
+  MEPOL_HIP((max_dynamic_lds<gemm_nt_kernel<WR, WC, FR, FC>>((int)P::kLds)));
   const int64_t tiles = (int64_t)((m + P::BN - 1) / P::BN) * ((n + P::BM - 1) / P::BM);
   hipLaunchKernelGGL((gemm_nt_kernel<WR, WC, FR, FC>), dim3((unsigned)tiles), dim3(P::kThreads), P::kLds, st, A,
                      n, k, lda, B, m, ldb, bias, relu, C, ldc);
@@ -472,10 +443,8 @@ extern "C" int mepol_gemm_nt(const double* A, int64_t n, int k, int64_t lda, con
 // [m, k] (dh1 = dz2 W2 = dz2 W2t^T, not materialised), the forward's h1 [n, m] and x [n, F].
 extern "C" int mepol_dh1_layer1_workspace_size(int64_t n, int m, int in_features,
                                                size_t* bytes) {
-  using namespace mepol::gemm::l1b;
   if (!bytes) return mepol::kErrBadArg;
-  *bytes = ((size_t)((n + P::BM - 1) / P::BM) + mepol::gemm::kGroups) * m * (in_features + 1) *
-           sizeof(double);
+  *bytes = mepol::gemm::l1b::ws_bytes(n, m, in_features);
   return 0;
 }
 
@@ -490,11 +459,12 @@ static int dh1_layer1_backward(const double* dz2, int64_t n, int k, const double
   if (n <= 0 || k <= 0 || (k & 1) || m <= 0 || F <= 0 || F > 63 || !dz2 || !W2t || !h1 || !x ||
       !dW1 || !workspace || ((uintptr_t)dz2 & 15) || ((uintptr_t)W2t & 15) || (BT && (m & 1))) {
     mepol::set_error("mepol_dh1_layer1_backward: bad arguments (k even, in_features <= 63, "
-                     "16-B aligned dz2 / W2t)");
+                     "16-B aligned dz2 / W2t%s)",
+                     BT ? "; the W2 form needs hidden0 even: 16-B aligned W2 rows" : "");
     return mepol::kErrBadArg;
   }
-  const int nrb = (int)((n + P::BM - 1) / P::BM);
-  const size_t need = ((size_t)nrb + mepol::gemm::kGroups) * m * (F + 1) * sizeof(double);
+  const int nrb = row_blocks(n);
+  const size_t need = ws_bytes(n, m, F);
   if (workspace_bytes < need) {
     mepol::set_error("mepol_dh1_layer1_backward: workspace %zu < %zu", workspace_bytes, need);
     return mepol::kErrWorkspace;
@@ -506,12 +476,7 @@ static int dh1_layer1_backward(const double* dz2, int64_t n, int k, const double
   const int nh = (F + 1 + 15) / 16;
 #define MEPOL_L1B(NHV)                                                                         \
   do {                                                                                         \
-    static bool attr = false;                                                                  \
-    if (!attr) {                                                                               \
-      MEPOL_HIP(hipFuncSetAttribute((const void*)dh1_layer1_bwd_kernel<NHV, MASK, BT>,         \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::kLds)); \
-      attr = true;                                                                             \
-    }                                                                                          \
+    MEPOL_HIP((mepol::max_dynamic_lds<dh1_layer1_bwd_kernel<NHV, MASK, BT>>((int)P::kLds)));   \
     hipLaunchKernelGGL((dh1_layer1_bwd_kernel<NHV, MASK, BT>), dim3(tiles), dim3(P::kThreads),  \
                        P::kLds, st,                                                            \
                        dz2, n, k, W2t, m, h1, x, F, part);                                     \
@@ -524,16 +489,7 @@ static int dh1_layer1_backward(const double* dz2, int64_t n, int k, const double
   }
 #undef MEPOL_L1B
   MEPOL_CHECK_LAUNCH();
-  const int64_t elems = (int64_t)m * (F + 1);
-  double* grp = part + (size_t)nrb * elems;
-  hipLaunchKernelGGL(mepol::gemm::layer1_reduce_kernel,
-                     dim3((unsigned)((elems + 63) / 64), mepol::gemm::kGroups), dim3(256), 0, st,
-                     part, nrb, m, F, grp);
-  MEPOL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mepol::gemm::layer1_reduce2_kernel, dim3((unsigned)((elems + 255) / 256)),
-                     dim3(256), 0, st, grp, m, F, dW1, db1);
-  MEPOL_CHECK_LAUNCH();
-  return 0;
+  return mepol::sum_records<kGroups>(part, nrb, (int64_t)m * (F + 1), ScatterW1{F, dW1, db1}, st);
 }
 
 extern "C" int mepol_dh1_layer1_backward(const double* dz2, int64_t n, int k, const double* W2t,

@@ -11,8 +11,11 @@
 // replaces the PyTorch sequence mean-GEMM, 6 elementwise kernels and a reduction in the forward,
 // and dX-GEMM, dW-GEMM, threshold_backward and the elementwise chain in the backward: the head
 // is HBM-bound (one pass over z forward; z read + dz written backward).
-// Reductions over rows go through per-block partials summed in a fixed order (deterministic).
-#include "common.hpp"
+// Reductions over rows go through per-block partials summed in a fixed order (deterministic):
+// the two-stage record sum of reduce.hpp.  The 16-lane reduce-scatter of the forward is
+// mfma::reduce_scatter_g (mfma_f64.hpp, shared with the fused forward's head epilogue).
+#include "mfma_f64.hpp"
+#include "reduce.hpp"
 
 #include <algorithm>
 
@@ -25,42 +28,9 @@ namespace head {
 
 constexpr int kMaxA = 32;     // fused path: action_dim <= 32 (MC 1, GW 2, Ant 8, Humanoid 17, HandReach 20)
 constexpr int kMaxCols = 8;   // columns per lane: hidden <= 512
-constexpr double kLog2Pi = 1.8378770664093453;
-constexpr double kStdEps = 1e-7;
-
-// Reduce-scatter of AP per-lane values over groups of G lanes (G a power of two <= 64, lanes
-// of a group consecutive): halving exchanges, then a butterfly over the remaining lanes.  Lane
-// l ends with the group's sum for component a_out; lanes of a group agreeing on the bits
-// log2(G)-1 .. log2(G)-log2(AP) hold the same component.
-template <int AP, int G>
-__device__ __forceinline__ double reduce_scatter_g(double (&v)[AP], int l, int& a_out) {
-  double cur[AP];
-#pragma unroll
-  for (int a = 0; a < AP; ++a) cur[a] = v[a];
-  int a_idx = 0;
-  int len = AP;
-  int bit = G / 2;
-#pragma unroll
-  for (int step = AP; step > 1; step >>= 1) {
-    const bool upper = (l & bit) != 0;
-    const int half = len >> 1;
-#pragma unroll
-    for (int a = 0; a < AP / 2; ++a) {
-      if (a < half) {
-        const double send = upper ? cur[a] : cur[a + half];
-        const double keep = upper ? cur[a + half] : cur[a];
-        cur[a] = keep + __shfl_xor(send, bit, kWave);
-      }
-    }
-    a_idx = a_idx * 2 + (upper ? 1 : 0);
-    len = half;
-    bit >>= 1;
-  }
-  double x = cur[0];
-  for (; bit >= 1; bit >>= 1) x += __shfl_xor(x, bit, kWave);
-  a_out = a_idx;
-  return x;
-}
+using mfma::kLog2Pi;
+using mfma::kStdEps;
+using mfma::reduce_scatter_g;
 
 // Forward with 16 lanes per row and 4 rows per wave: lane (r = l>>4, q = l&15) owns columns
 // c = q + 16 j (j < NCL) of row 4 i + r.  Each lane runs NCL x AP fma into AP accumulators; the
@@ -173,7 +143,7 @@ __device__ __forceinline__ double readlane_d(double v, int lane) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 
-// Per-block partial records [dW (A*H) | db (A) | dls (A)], reduced by reduce_partials_kernel.
+// Per-block partial records [dW (A*H) | db (A) | dls (A)], summed by sum_records.
 template <int AP, int NC>
 __global__ __launch_bounds__(256) void head_bwd_kernel(
     const double* __restrict__ gl, const double* __restrict__ z, int64_t N, int H,
@@ -335,8 +305,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(
 // chains independent work.  dmu is lane-distributed (lane a holds component a) and broadcast with
 // v_readlane; Wm sits in LDS as [a][Hs] (Hs = block width, dynamic LDS, AP * Hs doubles).  The
 // block walks rows in a fixed order (grid-stride), so each block's partial record
-// [dW (A*H) | db (A) | dls (A) | dbz (H)] is deterministic and reduce_partials_kernel sums the
-// records in a fixed order as for head_bwd_kernel.
+// [dW (A*H) | db (A) | dls (A) | dbz (H)] is deterministic and sum_records adds the records
+// in a fixed order as for head_bwd_kernel.
 
 template <int AP>
 __global__ __launch_bounds__(512) void head_bwd_wide_kernel(
@@ -448,61 +418,28 @@ __global__ __launch_bounds__(512) void head_bwd_wide_kernel(
   }
 }
 
-// out = sum_b part[b][:] in a fixed order: 64 elements per block, wave w sums a quarter of the
-// partials, the 4 quarter sums are added in order.  dW goes to dWm, the tail to dbm / dls.
-// Sum of the per-block partial records in two fixed-order stages (one block column per 64
-// elements with all records serial per wave was latency-bound, 35 us at C3): stage 1 sums
-// record group g (kRedGroups strided groups) for 64 elements per block, stage 2 sums the groups
-// in order and scatters into dWm | dbm | dls | dbz.
+// The per-block partial records are summed by sum_records (reduce.hpp) in kRedGroups strided
+// groups; element e of a record goes to dWm | dbm | dls | dbz.
 constexpr int kRedGroups = 8;
 
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const double* __restrict__ part,
-                                                              int nblocks, int64_t m,
-                                                              double* __restrict__ grp) {
-  __shared__ double sh[4][64];
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t e = (int64_t)blockIdx.x * 64 + l;
-  const int gi = blockIdx.y;
-  double s = 0.0;
-  if (e < m)
-    for (int b = gi + kRedGroups * w; b < nblocks; b += 4 * kRedGroups)
-      s += part[(int64_t)b * m + e];
-  sh[w][l] = s;
-  __syncthreads();
-  if (w == 0 && e < m) grp[(int64_t)gi * m + e] = ((sh[0][l] + sh[1][l]) + sh[2][l]) + sh[3][l];
-}
-
-__global__ __launch_bounds__(256) void reduce_groups_kernel(const double* __restrict__ grp,
-                                                            int64_t m, int AH, int A,
-                                                            double* __restrict__ dWm,
-                                                            double* __restrict__ dbm,
-                                                            double* __restrict__ dls,
-                                                            double* __restrict__ dbz) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= m) return;
-  double t = 0.0;
-#pragma unroll
-  for (int g = 0; g < kRedGroups; ++g) t += grp[(int64_t)g * m + e];
-  if (e < AH)
-    dWm[e] = t;
-  else if (e < AH + A)
-    dbm[e - AH] = t;
-  else if (e < AH + 2 * A)
-    dls[e - AH - A] = t;
-  else if (dbz)
-    dbz[e - AH - 2 * A] = t;
-}
+struct ScatterGrads {
+  int AH, A;
+  double *dWm, *dbm, *dls, *dbz;
+  __device__ void operator()(int64_t e, double t) const {
+    if (e < AH)
+      dWm[e] = t;
+    else if (e < AH + A)
+      dbm[e - AH] = t;
+    else if (e < AH + 2 * A)
+      dls[e - AH - A] = t;
+    else if (dbz)
+      dbz[e - AH - 2 * A] = t;
+  }
+};
 
 static int reduce_records(const double* part, int nb, int64_t m, int AH, int A, double* dWm,
                           double* dbm, double* dls, double* dbz, hipStream_t st) {
-  double* grp = const_cast<double*>(part) + (size_t)nb * m;
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((m + 63) / 64), kRedGroups),
-                     dim3(256), 0, st, part, nb, m, grp);
-  MEPOL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_groups_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                     grp, m, AH, A, dWm, dbm, dls, dbz);
-  MEPOL_CHECK_LAUNCH();
-  return 0;
+  return sum_records<kRedGroups>(part, nb, m, ScatterGrads{AH, A, dWm, dbm, dls, dbz}, st);
 }
 
 #ifndef MEPOL_HEAD_BWD_MAXB
@@ -511,6 +448,12 @@ static int reduce_records(const double* part, int nb, int64_t m, int AH, int A, 
 static int grid_bwd(int64_t N) {
   const int64_t waves = (N + 31) / 32;  // >= 32 rows per wave
   return (int)std::max<int64_t>(1, std::min<int64_t>(MEPOL_HEAD_BWD_MAXB, (waves + 3) / 4));
+}
+
+// one record [dW (A*H) | db (A) | dls (A) | dbz (H)] per block, then sum_records' group sums
+static size_t ws_bytes(int64_t n, int hidden, int a_dim) {
+  const size_t m = (size_t)a_dim * (hidden + 2) + hidden;
+  return sum_records_bytes<kRedGroups>(grid_bwd(std::max<int64_t>(n, 1)), m);
 }
 
 }  // namespace head
@@ -555,8 +498,7 @@ extern "C" int mepol_head_forward(const double* z, int64_t n, int hidden, const 
 
 extern "C" int mepol_head_workspace_size(int64_t n, int hidden, int a_dim, size_t* bytes) {
   if (!bytes || hidden <= 0 || a_dim <= 0) return kErrBadArg;
-  const int nb = grid_bwd(std::max<int64_t>(n, 1));
-  *bytes = ((size_t)nb + kRedGroups) * ((size_t)a_dim * (hidden + 2) + hidden) * sizeof(double);
+  *bytes = ws_bytes(n, hidden, a_dim);
   return 0;
 }
 
@@ -577,8 +519,7 @@ static int head_backward(const double* grad_logp, const double* z, int64_t n, in
     return kErrBadArg;
   }
   const int nb = grid_bwd(n);
-  const size_t need =
-      ((size_t)nb + kRedGroups) * ((size_t)a_dim * (hidden + 2) + hidden) * sizeof(double);
+  const size_t need = ws_bytes(n, hidden, a_dim);
   if (workspace_bytes < need) {
     set_error("mepol_head_backward: workspace %zu < %zu", workspace_bytes, need);
     return kErrWorkspace;
@@ -593,12 +534,7 @@ static int head_backward(const double* grad_logp, const double* z, int64_t n, in
     const size_t lds = ((size_t)apw * hs + (size_t)(hs / 64) * 2 * apw) * sizeof(double);
 #define MEPOL_HEAD_BWDW(AP_)                                                                    \
   if (apw == AP_) {                                                                             \
-    static bool attr_set = false;                                                               \
-    if (!attr_set) {                                                                            \
-      MEPOL_HIP(hipFuncSetAttribute((const void*)head_bwd_wide_kernel<AP_>,                     \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));   \
-      attr_set = true;                                                                          \
-    }                                                                                           \
+    MEPOL_HIP(max_dynamic_lds<head_bwd_wide_kernel<AP_>>(160 * 1024));                          \
     hipLaunchKernelGGL((head_bwd_wide_kernel<AP_>), dim3(nb), dim3(hs), lds, st, grad_logp, z, n, \
                        hidden, hs, bz, Wm, log_std, act, mu, a_dim, dz, pdW);                   \
   }

@@ -140,6 +140,17 @@ __global__ void layer_reduce_kernel(const double* __restrict__ part, int nb, int
 
 constexpr int kRowBlocks = 256;  // upper bound on row-chunk blocks per column tile
 
+// the most row blocks a launch over n rows uses: row_blocks() never returns more
+inline int max_row_blocks(int64_t n) {
+  return (int)std::min<int64_t>(kRowBlocks, std::max<int64_t>((n + kChunk - 1) / kChunk, 1));
+}
+
+// layer_bwd_kernel's partial records [row block][H][F + 1], sized for max_row_blocks(n): the
+// launcher's grid depends on the device, the size entry point must not
+inline size_t ws_bytes(int64_t n, int H, int F) {
+  return (size_t)max_row_blocks(n) * H * (F + 1) * sizeof(double);
+}
+
 // Blocks per column tile so that the whole grid is resident at once (no partial second wave of
 // blocks): CUs x resident blocks per CU / column tiles, capped by kRowBlocks and the chunks.
 // The device queries are cached (first call per kernel/device), so launches made under HIP
@@ -166,9 +177,8 @@ int row_blocks(Kernel kernel, int64_t n, int col_tiles) {
     }
     resident = it->second;
   }
-  const int64_t chunks = std::max<int64_t>((n + kChunk - 1) / kChunk, 1);
   const int64_t fit = std::max<int64_t>((int64_t)resident / col_tiles, 1);
-  return (int)std::min<int64_t>(std::min<int64_t>(fit, kRowBlocks), chunks);
+  return (int)std::min<int64_t>(fit, max_row_blocks(n));
 }
 
 }  // namespace mlp
@@ -221,8 +231,7 @@ extern "C" int mepol_layer_forward(const double* x, int64_t n, int in_features, 
 extern "C" int mepol_layer_workspace_size(int64_t n, int in_features, int out_features,
                                           size_t* bytes) {
   if (!bytes || in_features <= 0 || out_features <= 0) return kErrBadArg;
-  const int gx = (int)std::min<int64_t>(kRowBlocks, std::max<int64_t>((n + kChunk - 1) / kChunk, 1));
-  *bytes = (size_t)gx * out_features * (in_features + 1) * sizeof(double);
+  *bytes = ws_bytes(n, out_features, in_features);
   return 0;
 }
 
@@ -238,7 +247,7 @@ extern "C" int mepol_layer_backward(const double* dh, const double* h, const dou
   const int gy = (out_features + 63) / 64;
   int gx = 1;
   MEPOL_FP_SWITCH(in_features, gx = row_blocks(layer_bwd_kernel<FP>, n, gy));
-  const size_t need = (size_t)gx * out_features * (in_features + 1) * sizeof(double);
+  const size_t need = ws_bytes(n, out_features, in_features);  // gx <= max_row_blocks(n)
   if (workspace_bytes < need) {
     set_error("mepol_layer_backward: workspace %zu < %zu", workspace_bytes, need);
     return kErrWorkspace;

@@ -22,10 +22,19 @@
 // read straight from L2 into the MFMA fragments: no LDS staging, no barrier in the K loop, and
 // this kernel's head epilogue).  C3: 1.19 ms against 1.32 for the one-kernel form below, which
 // stays for odd h0 (profiles/r5/f64/forward_split_ab.txt).
-#include "common.hpp"
+//
+// From mfma_f64.hpp: the one-kernel form's head epilogue (mfma::head_epilogue; z2_head_kernel
+// keeps its own 4-action copy, see there), the lane exchange of both epilogues
+// (mfma::reduce_scatter_g) and z2_head_kernel's K loop (mfma::ring_k_loop).
+#include "mfma_f64.hpp"
 
 namespace mepol {
 namespace pfwd {
+
+using mfma::d4;
+using mfma::head_epilogue;
+using mfma::kLog2Pi;
+using mfma::kStdEps;
 
 constexpr int BM = 64, BN = 320;     // output tile (rows x h1 columns)
 constexpr int WC = 4;                // column waves (80 columns each); 2 row waves (32 rows)
@@ -34,10 +43,8 @@ constexpr int kThreads = 512;
 constexpr int KT = 16, KP = 18;      // k-tile and padded LDS row (doubles)
 constexpr int CB = BN * (KT / 2), PB = CB / kThreads;  // 16-B chunks of a W2 k-tile per thread
 constexpr int kAChunk = 8;           // actions per epilogue pass
-constexpr double kLog2Pi = 1.8378770664093453;
-constexpr double kStdEps = 1e-7;
-typedef double d4 __attribute__((ext_vector_type(4)));
 static_assert(CB % kThreads == 0, "W2 k-tile chunks must divide the block");
+static_assert(kThreads == BM * kAChunk, "head_epilogue: one thread per (row, action slot)");
 
 template <int FP>
 constexpr size_t lds_bytes() {
@@ -212,96 +219,10 @@ __global__ __launch_bounds__(kThreads) void policy_fwd_kernel(
     __syncthreads();
   }
 
-  // ---- epilogue: z2 out, then the head on relu(z2 + b2) -----------------------------------
-  // C/D map of the f64 16x16x4 MFMA: col = lane & 15, row = (lane >> 4) + 4 q.
-  double b2v[FC];
-#pragma unroll
-  for (int j = 0; j < FC; ++j) {
-    const int c = wc * FC * 16 + j * 16 + fr;
-    b2v[j] = c < H2 ? b2[c] : 0.0;
-#pragma unroll
-    for (int i = 0; i < FR; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t r = row0 + wr * FR * 16 + i * 16 + g + 4 * q;
-        if (c < H2 && r < N) z2_out[r * H2 + c] = acc[i][j][q];
-      }
-  }
-  double* sMu = sB;  // [WC][BM][kAChunk]; the loop's last barrier retired every sB read
-  const int er = tid >> 3, ea = tid & 7;  // combine step: row er of the block, action slot ea
-  double lp = 0.0;
-  for (int a0 = 0; a0 < A; a0 += kAChunk) {
-    double wmv[FC][kAChunk];
-#pragma unroll
-    for (int j = 0; j < FC; ++j) {
-      const int c = wc * FC * 16 + j * 16 + fr;
-#pragma unroll
-      for (int a = 0; a < kAChunk; ++a)
-        wmv[j][a] = (c < H2 && a0 + a < A) ? Wm[(int64_t)(a0 + a) * H2 + c] : 0.0;
-    }
-#pragma unroll
-    for (int i = 0; i < FR; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        double p[kAChunk];
-#pragma unroll
-        for (int a = 0; a < kAChunk; ++a) p[a] = 0.0;
-#pragma unroll
-        for (int j = 0; j < FC; ++j) {
-          const double rv = fmax(acc[i][j][q] + b2v[j], 0.0);
-#pragma unroll
-          for (int a = 0; a < kAChunk; ++a) p[a] = fma(rv, wmv[j][a], p[a]);
-        }
-        // reduce-scatter over the 16 lanes of the row: halving exchanges on lane bits 8, 4, 2
-        // leave lane l with component ((l>>3)&1)*4 + ((l>>2)&1)*2 + ((l>>1)&1), then bit 1
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const bool up = (fr & 8) != 0;
-          const double send = up ? p[a] : p[a + 4];
-          p[a] = (up ? p[a + 4] : p[a]) + __shfl_xor(send, 8, kWave);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          const bool up = (fr & 4) != 0;
-          const double send = up ? p[a] : p[a + 2];
-          p[a] = (up ? p[a + 2] : p[a]) + __shfl_xor(send, 4, kWave);
-        }
-        {
-          const bool up = (fr & 2) != 0;
-          const double send = up ? p[0] : p[1];
-          p[0] = (up ? p[1] : p[0]) + __shfl_xor(send, 2, kWave);
-        }
-        p[0] += __shfl_xor(p[0], 1, kWave);
-        const int comp = ((fr >> 3) & 1) * 4 + ((fr >> 2) & 1) * 2 + ((fr >> 1) & 1);
-        if ((fr & 1) == 0) {
-          const int rl = wr * FR * 16 + i * 16 + g + 4 * q;
-          sMu[(wc * BM + rl) * kAChunk + comp] = p[0];
-        }
-      }
-    __syncthreads();
-    {
-      const int a = a0 + ea;
-      const int64_t r = row0 + er;
-      double term = 0.0;
-      if (a < A && r < N) {
-        double m = sMu[(0 * BM + er) * kAChunk + ea];
-#pragma unroll
-        for (int w = 1; w < WC; ++w) m += sMu[(w * BM + er) * kAChunk + ea];
-        m += bm[a];
-        const double lsa = log_std[a];
-        const double sd = exp(lsa) + kStdEps;
-        const double d = act[r * A + a] - m;
-        mu_out[r * A + a] = m;
-        term = -0.5 * (kLog2Pi + 2.0 * lsa + d * d / (sd * sd));
-      }
-      term += __shfl_xor(term, 4, kWave);
-      term += __shfl_xor(term, 2, kWave);
-      term += __shfl_xor(term, 1, kWave);
-      lp += term;
-    }
-    __syncthreads();
-  }
-  if (ea == 0 && row0 + er < N) logp_out[row0 + er] = lp;
+  // ---- epilogue: z2 out, then the head on relu(z2 + b2), 8 actions per pass ------------------
+  // sMu [WC][BM][8] reuses sB: the loop's last barrier retired every sB read
+  head_epilogue<FR, FC, kAChunk, WC, BM>(acc, row0, wr * FR * 16, wc, N, b2, H2, Wm, bm, log_std,
+                                         act, A, z2_out, mu_out, logp_out, sB);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -384,8 +305,8 @@ __global__ __launch_bounds__(256) void layer1_kernel(const double* __restrict__ 
 // [80 w, 80 w + 80) (4 x 5 fragments) and reads both operands straight from L2 into the MFMA
 // fragments -- a lane takes 16 B of its row per fragment, k = 8 st + 2 g + {0, 1}, and the
 // stage's two k-steps use the two halves (h1 and W2 in the same k order).  No LDS staging and
-// no barrier in the K loop; the head epilogue is the fused kernel's (LDS only for the sum of
-// the 4 column waves).  tools/z2_probe.py: the bare GEMM at 50.7 TF/s (C3) against 45 in the
+// no barrier in the K loop; LDS only for the head epilogue's sum of the 4 column waves.
+// tools/z2_probe.py: the bare GEMM at 50.7 TF/s (C3) against 45 in the
 // fused kernel's k-tile loop.
 namespace zh {
 constexpr int FO = 4, FI = 5, NW = 4, NS = 2, NL = FO + FI;
@@ -438,30 +359,19 @@ __global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(2))
       for (int u = 0; u < FI; ++u)
         acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(D[t].y, D[FO + u].y, acc[t][u], 0, 0, 0);
   };
+  mfma::ring_k_loop<NS>(
+      nfull, nst, [&](int p, int st) __attribute__((always_inline)) { load(R[p], st); },
+      [&](int p, int st) __attribute__((always_inline)) {
+        if (8 * st + 2 * g >= H1) {  // the tail stage's missing pairs
 #pragma unroll
-  for (int p = 0; p < NS - 1; ++p) load(R[p], min(p, nst - 1));
-  int st = 0;
-#pragma nounroll
-  for (; st + NS <= nfull; st += NS) {
-#pragma unroll
-    for (int p = 0; p < NS; ++p) {
-      load(R[(p + NS - 1) % NS], min(st + p + NS - 1, nst - 1));
-      mma(R[p]);
-    }
-  }
-#pragma unroll
-  for (int p = 0; p < NS; ++p) {
-    if (st + p < nst) {  // uniform
-      if (st + p + NS - 1 < nst) load(R[(p + NS - 1) % NS], st + p + NS - 1);
-      if (st + p >= nfull && 8 * (st + p) + 2 * g >= H1) {  // the tail stage's missing pairs
-#pragma unroll
-        for (int v = 0; v < NL; ++v) R[p][v] = double2{0.0, 0.0};
-      }
-      mma(R[p]);
-    }
-  }
+          for (int v = 0; v < NL; ++v) R[p][v] = double2{0.0, 0.0};
+        }
+      },
+      [&](int p) __attribute__((always_inline)) { mma(R[p]); });
 
-  // ---- epilogue: z2 out, then the head on relu(z2 + b2) (as policy_fwd_kernel's) ----------
+  // ---- epilogue: z2 out, then the head on relu(z2 + b2) ------------------------------------
+  // A local copy of mfma::head_epilogue<FO, FI, 4, NW, ZM> (only the lane exchange is shared):
+  // through the template this kernel, at its 256-VGPR budget, compiled to 36 spilled VGPRs.
   double b2v[FI];
 #pragma unroll
   for (int u = 0; u < FI; ++u) {
@@ -476,7 +386,7 @@ __global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(2))
       }
   }
   // 4 actions per pass (the fused kernel's 8 would hold 40 more registers next to the 160 of
-  // the accumulators): reduce-scatter over lane bits 8 and 4, sum over bits 2 and 1
+  // the accumulators)
   constexpr int AC = 4;
   const int er = tid >> 2, ea = tid & 3;  // combine step: row er of the block, action slot ea
   double lp = 0.0;
@@ -502,21 +412,9 @@ __global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(2))
 #pragma unroll
           for (int a = 0; a < AC; ++a) p[a] = fma(rv, wmv[u][a], p[a]);
         }
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          const bool up = (fr & 8) != 0;
-          const double send = up ? p[a] : p[a + 2];
-          p[a] = (up ? p[a + 2] : p[a]) + __shfl_xor(send, 8, kWave);
-        }
-        {
-          const bool up = (fr & 4) != 0;
-          const double send = up ? p[0] : p[1];
-          p[0] = (up ? p[1] : p[0]) + __shfl_xor(send, 4, kWave);
-        }
-        p[0] += __shfl_xor(p[0], 2, kWave);
-        p[0] += __shfl_xor(p[0], 1, kWave);
-        const int comp = ((fr >> 3) & 1) * 2 + ((fr >> 2) & 1);
-        if ((fr & 3) == 0) sMu[(w * ZM + 16 * t + g + 4 * q) * AC + comp] = p[0];
+        int comp;
+        const double v = mfma::reduce_scatter_g<AC, 16>(p, fr, comp);
+        if ((fr & 3) == 0) sMu[(w * ZM + 16 * t + g + 4 * q) * AC + comp] = v;
       }
     __syncthreads();
     {
@@ -569,13 +467,7 @@ int launch(const double* x, int64_t n, int F, const double* W1, const double* b1
            const double* W2, const double* b2, int H2, const double* Wm, const double* bm,
            const double* log_std, const double* act, int A, double* h1, double* z2, double* mu,
            double* logp, uint16_t* mask, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    MEPOL_HIP(hipFuncSetAttribute((const void*)policy_fwd_kernel<FP, VEC>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_bytes<FP>()));
-    attr = true;
-  }
+  MEPOL_HIP((max_dynamic_lds<policy_fwd_kernel<FP, VEC>>((int)lds_bytes<FP>())));
   const unsigned blocks = (unsigned)((n + BM - 1) / BM);
   hipLaunchKernelGGL((policy_fwd_kernel<FP, VEC>), dim3(blocks), dim3(kThreads), lds_bytes<FP>(), st,
                      x, n, F, W1, b1, H1, W2, b2, H2, Wm, bm, log_std, act, A, h1, z2, mu, logp,

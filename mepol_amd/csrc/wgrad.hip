@@ -10,18 +10,24 @@
 // output block (20 accumulators) over one K-slice, with the fragments of the next k-step
 // in flight; the K-slices' partial blocks are summed in a fixed order by a second launch (the
 // same bits every run).  The tiles of one K-slice are dispatched back to back onto one XCD, so
-// its rows come from HBM once and from that XCD's L2 for the other tiles.
+// its rows come from HBM once and from that XCD's L2 for the other tiles.  (That slice -> XCD
+// map is not mfma::xcd_tile, which keeps the column tiles of one row block together: here the
+// unit that shares rows is a whole K-slice, and slices, not tiles, are dealt round the XCDs.)
+// d4 and the fragment map come from mfma_f64.hpp, and the K loop is its ring_k_loop, shared with
+// z2_head_kernel (policy_fwd.hip).
 //
 // Replaces rocBLAS's split-K bmm + torch.sum (policy._weight_grad) on the off-policy
 // iteration's dW2: 1.04 ms + reduce at C3 (46 TF/s on 48 GF).
-#include "common.hpp"
+#include "mfma_f64.hpp"
 
 #include <algorithm>
 
 namespace mepol {
 namespace wgrad {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
+using mfma::d4;
+using mfma::frag_col;
+using mfma::frag_row;
 constexpr int FO = 4, FI = 5;      // 16 x 16 fragments per wave: 64 (o) x 80 (i)
 constexpr int kOcc = 2;            // waves per SIMD (VGPR budget 256)
 constexpr int BO = 16 * FO, BI = 16 * FI;
@@ -43,6 +49,11 @@ inline int slices_for(int64_t n, int O, int I) {
   return (int)std::min<int64_t>(kMaxSlices, s & ~7);
 }
 
+// the K-slices' partial blocks
+inline size_t ws_bytes(int64_t n, int O, int I) {
+  return (size_t)slices_for(n, O, I) * O * I * sizeof(double);
+}
+
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kOcc))) void wgrad_kernel(
     const double* __restrict__ dy, int64_t n, int O, const double* __restrict__ x, int I,
     int nob, int nib, int S, int64_t slice_rows, double* __restrict__ part) {
@@ -61,9 +72,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kOcc))) void
   if (r_begin >= r_end) {  // an empty slice still owns its partial block: zeros
     for (int t = 0; t < FO; ++t)
       for (int q = 0; q < 4; ++q) {
-        const int o = ob * BO + 16 * t + g + 4 * q;
+        const int o = ob * BO + 16 * t + frag_row(l, q);
         for (int u = 0; u < FI; ++u) {
-          const int i = ib * BI + 16 * u + fr;
+          const int i = ib * BI + 16 * u + frag_col(l);
           if (o < O && i < I) part[((int64_t)s * O + o) * I + i] = 0.0;
         }
       }
@@ -102,42 +113,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kOcc))) void
         acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(D[t], D[FO + u], acc[t][u], 0, 0, 0);
   };
   const int64_t rows = r_end - r_begin;
-  const int64_t nfull = rows / 4;               // k-steps with 4 rows in the slice
+  const int64_t nfull = rows / 4;  // k-steps with 4 rows in the slice
   const int64_t nks = (rows + 3) / 4;
-#pragma unroll
-  for (int p = 0; p < NS - 1; ++p) load(R[p], min<int64_t>(p, nks - 1));
-  int64_t ks = 0;
-  // steady state, unrolled by NS (compile-time ring slots): k-step ks is in R[ks % NS]
-#pragma nounroll
-  for (; ks + NS <= nfull; ks += NS) {
-#pragma unroll
-    for (int p = 0; p < NS; ++p) {
-      load(R[(p + NS - 1) % NS], min<int64_t>(ks + p + NS - 1, nks - 1));
-      mma(R[p]);
-    }
-  }
-  // the remaining (< NS) full k-steps and the ragged last one, in the same ring rotation
-#pragma unroll
-  for (int p = 0; p < NS; ++p) {
-    if (ks + p < nks) {  // uniform
-      if (ks + p + NS - 1 < nks) load(R[(p + NS - 1) % NS], ks + p + NS - 1);
-      if (ks + p >= nfull) {  // ragged: rows past the slice end contribute zero
-        const bool ok = r_begin + 4 * (ks + p) + g < r_end;
+  mfma::ring_k_loop<NS>(
+      nfull, nks, [&](int p, int64_t ks) __attribute__((always_inline)) { load(R[p], ks); },
+      [&](int p, int64_t ks) __attribute__((always_inline)) {
+        const bool ok = r_begin + 4 * ks + g < r_end;  // rows past the slice end contribute zero
 #pragma unroll
         for (int v = 0; v < NL; ++v) R[p][v] = ok ? R[p][v] : 0.0;
-      }
-      mma(R[p]);
-    }
-  }
-  // C/D map of the f64 16x16x4 MFMA: col = lane & 15, row = (lane >> 4) + 4 q
+      },
+      [&](int p) __attribute__((always_inline)) { mma(R[p]); });
 #pragma unroll
   for (int t = 0; t < FO; ++t)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int o = ob * BO + 16 * t + g + 4 * q;
+      const int o = ob * BO + 16 * t + frag_row(l, q);
 #pragma unroll
       for (int u = 0; u < FI; ++u) {
-        const int i = ib * BI + 16 * u + fr;
+        const int i = ib * BI + 16 * u + frag_col(l);
         if (o < O && i < I) part[((int64_t)s * O + o) * I + i] = acc[t][u][q];
       }
     }
@@ -166,8 +159,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const double* __restr
 extern "C" int mepol_weight_grad_workspace_size(int64_t n, int out_features, int in_features,
                                                 size_t* bytes) {
   if (!bytes || n < 0 || out_features <= 0 || in_features <= 0) return mepol::kErrBadArg;
-  *bytes = (size_t)mepol::wgrad::slices_for(n, out_features, in_features) * out_features *
-           in_features * sizeof(double);
+  *bytes = mepol::wgrad::ws_bytes(n, out_features, in_features);
   return 0;
 }
 
@@ -181,7 +173,7 @@ extern "C" int mepol_weight_grad(const double* dy, int64_t n, int out_features, 
     return mepol::kErrBadArg;
   }
   const int S = slices_for(n, O, I);
-  const size_t need = (size_t)S * O * I * sizeof(double);
+  const size_t need = ws_bytes(n, O, I);
   if (workspace_bytes < need) {
     mepol::set_error("mepol_weight_grad: workspace %zu < %zu", workspace_bytes, need);
     return mepol::kErrWorkspace;

@@ -4,6 +4,7 @@ Every function here launches HIP kernels from libmepol_amd.so; none has a CPU pa
 must live on a ROCm device; dtypes follow the reference (f64 values, int64 indices at the
 API boundary; int32 indices internally).
 """
+import ctypes
 import math
 import threading
 
@@ -20,8 +21,6 @@ def _stream():
 
 
 def ctypes_void(v):
-    import ctypes
-
     return ctypes.c_void_p(v)
 
 
@@ -45,36 +44,38 @@ def _workspace(device, nbytes, tag="knn"):
     return buf
 
 
+def _ws_bytes(op, *sizes):
+    """Bytes of scratch mepol_<op> needs at these sizes (its mepol_<op>_workspace_size)."""
+    nbytes = ctypes.c_size_t()
+    call(f"mepol_{op}_workspace_size", *sizes, ctypes.byref(nbytes))
+    return nbytes.value
+
+
+def _own_workspace(device, op, *sizes):
+    return torch.empty(max(_ws_bytes(op, *sizes), 1), dtype=torch.uint8, device=device)
+
+
+def _ws_or_cached(ws, device, tag, op, *sizes):
+    """The caller's `ws`, or the per-stream eager buffer `tag` grown to what mepol_<op> needs."""
+    return ws if ws is not None else _workspace(device, _ws_bytes(op, *sizes), tag=tag)
+
+
 def head_workspace(n, hidden, a, device):
     """A caller-owned scratch buffer for head_backward at these sizes."""
-    import ctypes
-
-    nbytes = ctypes.c_size_t()
-    call("mepol_head_workspace_size", n, hidden, a, ctypes.byref(nbytes))
-    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=device)
+    return _own_workspace(device, "head", n, hidden, a)
 
 
 def layer_workspace(n, f, out, device):
     """A caller-owned scratch buffer for layer_backward at these sizes."""
-    import ctypes
-
-    nbytes = ctypes.c_size_t()
-    call("mepol_layer_workspace_size", n, f, out, ctypes.byref(nbytes))
-    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=device)
+    return _own_workspace(device, "layer", n, f, out)
 
 
 def dh1_layer1_workspace(n, h0, f, device):
     """A caller-owned scratch buffer for dh1_layer1_backward at these sizes."""
-    import ctypes
-
-    nbytes = ctypes.c_size_t()
-    call("mepol_dh1_layer1_workspace_size", n, h0, f, ctypes.byref(nbytes))
-    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=device)
+    return _own_workspace(device, "dh1_layer1", n, h0, f)
 
 
 def knn_plan(n_cand, n_query, d, kp1, split=0):
-    import ctypes
-
     ks, lst, sp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     call("mepol_knn_plan_info", n_cand, n_query, d, kp1, split, ctypes.byref(ks),
          ctypes.byref(lst), ctypes.byref(sp))
@@ -170,8 +171,6 @@ def knn(cand, kp1, query=None, split=0, want_int64=True, return_fallback=False, 
     is appended to the result and the caller must call its raise_if_invalid() before using it.
     Replaces NearestNeighbors(k+1).fit(X).kneighbors(X) (src/algorithms/mepol.py:190-192).
     """
-    import ctypes
-
     if query is None:
         query = cand
     _require_device(cand, query)
@@ -182,9 +181,7 @@ def knn(cand, kp1, query=None, split=0, want_int64=True, return_fallback=False, 
     if query.shape[1] != d:
         raise ValueError("query/candidate dimension mismatch")
     dev = cand.device
-    nbytes = ctypes.c_size_t()
-    call("mepol_knn_workspace_size", nc, nq, d, kp1, split, ctypes.byref(nbytes))
-    ws = _workspace(dev, nbytes.value)
+    ws = _ws_or_cached(None, dev, "knn", "knn", nc, nq, d, kp1, split)
     D = torch.empty((nq, kp1), dtype=torch.float64, device=dev)
     I = torch.empty((nq, kp1), dtype=torch.int64, device=dev) if want_int64 else None
     I32T = torch.empty((kp1, nq), dtype=torch.int32, device=dev)
@@ -292,15 +289,11 @@ def sharded_emit(x_all, world, stride, off, B, n_global, sums_cur, vals):
 
 def csr_build(idxT, k, n_own, col_offset=0, row_offset=0, nq=None):
     """CSR transpose of the first k rows of idxT ([>=k, nq]) for ids [col_offset, +n_own)."""
-    import ctypes
-
     _require_device(idxT)
     if nq is None:
         nq = idxT.shape[1]
     dev = idxT.device
-    nbytes = ctypes.c_size_t()
-    call("mepol_csr_workspace_size", nq, k, n_own, ctypes.byref(nbytes))
-    ws = _workspace(dev, nbytes.value, tag="csr")
+    ws = _ws_or_cached(None, dev, "csr", "csr", nq, k, n_own)
     off = torch.empty(n_own + 1, dtype=torch.int32, device=dev)
     rows = torch.empty(max(nq * k, 1), dtype=torch.int32, device=dev)
     call("mepol_csr_build", ptr(idxT), nq, k, col_offset, n_own, row_offset, ptr(off), ptr(rows),
@@ -355,15 +348,10 @@ def head_backward(grad_logp, z, Wm, log_std, act, mu, bz=None, need_dz=True, ws=
     `defer_reduce`: only the row kernel runs now; a sixth return value finish() launches the
     reduces on the then-current stream, which must be ordered after this one and before the
     workspace is reused."""
-    import ctypes
-
     n, h = z.shape
     a = Wm.shape[0]
     dev = z.device
-    if ws is None:
-        nbytes = ctypes.c_size_t()
-        call("mepol_head_workspace_size", n, h, a, ctypes.byref(nbytes))
-        ws = _workspace(dev, nbytes.value, tag="head")
+    ws = _ws_or_cached(ws, dev, "head", "head", n, h, a)
     dz = torch.empty_like(z) if need_dz else None
     if outs is not None:
         dWm, dbm, dls, dbz = outs
@@ -459,12 +447,7 @@ def dh1_layer1_backward(dz2, W2t, h1, x, ws=None, dW_out=None, db_out=None, mask
     else:
         h0 = W2t.shape[0]
         assert W2t.shape[1] == k and h1.shape == (n, h0) and dz2.is_contiguous() and W2t.is_contiguous()
-    if ws is None:
-        import ctypes
-
-        nbytes = ctypes.c_size_t()
-        call("mepol_dh1_layer1_workspace_size", n, h0, f, ctypes.byref(nbytes))
-        ws = _workspace(x.device, nbytes.value, tag="dh1l1")
+    ws = _ws_or_cached(ws, x.device, "dh1l1", "dh1_layer1", n, h0, f)
     dW = dW_out if dW_out is not None else torch.empty((h0, f), dtype=torch.float64,
                                                       device=x.device)
     db = db_out if db_out is not None else torch.empty(h0, dtype=torch.float64, device=x.device)
@@ -485,11 +468,7 @@ def dh1_layer1_backward(dz2, W2t, h1, x, ws=None, dW_out=None, db_out=None, mask
 
 def weight_grad_workspace(n, out_features, in_features, device):
     """Scratch of weight_grad (its K-slices' partial blocks), owned by the caller."""
-    import ctypes
-
-    nbytes = ctypes.c_size_t()
-    call("mepol_weight_grad_workspace_size", n, out_features, in_features, ctypes.byref(nbytes))
-    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=device)
+    return _own_workspace(device, "weight_grad", n, out_features, in_features)
 
 
 def weight_grad(dy, x, out=None, ws=None):
@@ -531,14 +510,9 @@ def layer_forward(x, W, b, out=None):
 def layer_backward(dh, h, x, ws=None):
     """(dW, db) of h = relu(x W^T + b) from dL/dh and the forward output h.  `ws`: caller-owned
     scratch (layer_workspace); default: the per-stream eager cache."""
-    import ctypes
-
     n, f = x.shape
     out = h.shape[1]
-    if ws is None:
-        nbytes = ctypes.c_size_t()
-        call("mepol_layer_workspace_size", n, f, out, ctypes.byref(nbytes))
-        ws = _workspace(x.device, nbytes.value, tag="layer")
+    ws = _ws_or_cached(ws, x.device, "layer", "layer", n, f, out)
     dW = torch.empty((out, f), dtype=torch.float64, device=x.device)
     db = torch.empty(out, dtype=torch.float64, device=x.device)
     call("mepol_layer_backward", ptr(dh), ptr(h), ptr(x), n, f, out, ptr(dW), ptr(db), ptr(ws),
@@ -550,8 +524,6 @@ def optim_step(kind, params, grads, exp_avg, exp_avg_sq, scalars, snapshot=None)
     """In-place Adam (kind 0) / RMSprop (kind 1) update of f64 tensors; scalars is a device f64
     tensor (see include/mepol_amd.h, mepol_optim_step).  snapshot = (params_snap, exp_avg_snap,
     exp_avg_sq_snap) lists (entries may be None) receive the values from before the update."""
-    import ctypes
-
     n = len(params)
     arr = ctypes.c_void_p * n
     snaps = list(snapshot) if snapshot is not None else [None, None, None]
@@ -603,11 +575,7 @@ def rollout_mlp(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, states_rec
     W2t = W2.t().contiguous()
     init64 = init.contiguous() if env_id == 0 else None
     init32 = init.contiguous() if env_id == 1 else None
-    import ctypes
-
-    nbytes = ctypes.c_size_t()
-    call("mepol_rollout_mlp_workspace_size", n, T, h0, h1, a_dim, ctypes.byref(nbytes))
-    ws = _workspace(init.device, nbytes.value, tag="rollout")
+    ws = _ws_or_cached(None, init.device, "rollout", "rollout_mlp", n, T, h0, h1, a_dim)
     args = (env_id, ptr(W1.contiguous()), ptr(b1), h0, ptr(W2t), ptr(b2), h1,
             ptr(Wm.contiguous()), ptr(bm), ptr(log_std.contiguous()), a_dim, ptr(init64),
             ptr(init32), ptr(noise.contiguous()), n, T, ptr(states_rec), ptr(actions_rec),
@@ -627,8 +595,6 @@ def rollout_mlp(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, states_rec
 def rollout_mlp_plan(n, h0, h1, a_dim):
     """{"workgroups_per_traj", "k_chunks"}: the form mepol_rollout_mlp takes for this shape and
     the layer-2 summation order it commits to (oracle.rollout_kordered's k_chunks)."""
-    import ctypes
-
     wg, kc = ctypes.c_int(), ctypes.c_int()
     call("mepol_rollout_mlp_plan_info", n, h0, h1, a_dim, ctypes.byref(wg), ctypes.byref(kc))
     return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}

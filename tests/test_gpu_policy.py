@@ -85,12 +85,16 @@ def test_predict_matches_forward(cuda):
 @pytest.mark.parametrize("n,nf,hidden,a", [(1000, 29, [400, 300], 8), (777, 2, [300, 300], 2),
                                            (513, 47, [400, 300], 17), (300, 63, [400, 300], 20),
                                            (100, 5, [37, 45], 3), (65, 1, [16, 320], 32),
-                                           (64, 33, [401, 17], 9), (1, 4, [8, 8], 1)])
+                                           (64, 33, [401, 17], 9), (1, 4, [8, 8], 1),
+                                           (33, 3, [2, 16], 2), (33, 3, [6, 33], 5),
+                                           (130, 7, [10, 81], 4), (70, 9, [18, 320], 12)])
 def test_policy_forward_kernel_matches_torch(cuda, n, nf, hidden, a):
     """mepol_policy_forward (csrc/policy_fwd.hip) == the nn.Linear / ReLU / Gaussian
     log-density math of src/policy.py:21-51 in torch f64.  Even h0 runs the split form
     (layer1_kernel + z2_head_kernel, including the 300-wide K tail); odd h0 (37, 401) the
-    one-kernel form."""
+    one-kernel form.  h0 = 2, 6, 10, 18 give the split form's K ring no full stage, a lone tail
+    stage with zeroed lane groups, and an odd stage count with a ragged tail; odd h1 (33, 81)
+    the column guards of the head epilogue."""
     from mepol_amd import ops
     from mepol_amd import policy as P
 

@@ -279,6 +279,21 @@ int mepol_gemm_nt(const double* A, int64_t n, int k, int64_t lda, const double* 
                   int64_t ldb, const double* bias, int relu, double* C, int64_t ldc, int variant,
                   void* stream);
 
+/* Backward through a hidden layer h_out = relu(h_in W^T + b) given dz_out = dL/d(pre-activation
+ * of h_out) [n, out_features]: dz_in [n, in_features] = (dz_out W) * (h_in > 0), the gradient at
+ * the previous layer's pre-activation (h_in [n, in_features] is that layer's ReLU output), and
+ * db_in [in_features] (nullable) = the column sums of dz_in, the previous layer's bias gradient.
+ * W [out_features, in_features] is the Linear weight as stored (no W^T copy).  The GEMM runs on
+ * the f64 matrix cores; db_in is summed in a fixed order (the same bits on every call).
+ * out_features and in_features even, dz_out and W 16-byte aligned; workspace from
+ * mepol_hidden_backward_workspace_size.  Replaces the torch.mm + threshold_backward + bias sum of
+ * a hidden layer in loss.backward() (src/policy.py:21-26, mepol.py:278) for policies with three
+ * or more hidden layers. */
+int mepol_hidden_backward_workspace_size(int64_t n, int in_features, size_t* bytes);
+int mepol_hidden_backward(const double* dz_out, int64_t n, int out_features, const double* W,
+                          const double* h_in, int in_features, double* dz_in, double* db_in,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- environments -------------------------------------------------------------------------
  * Replace MountainCarContinuous.step (src/envs/mountain_car_wall.py:13-45) and
  * GridWorldContinuous.step (src/envs/gridworld_continuous.py:128-154), batched. */
@@ -294,7 +309,7 @@ int mepol_rollout_step(int env_id, double* env_f64, float* env_f32, const double
 
 /* ---- Optimizer step of policy_update (mepol.py:280, optimizer.step()) ------------------------
  * Replaces torch.optim.Adam(lr).step() (kind 0) / torch.optim.RMSprop(lr).step() (kind 1) as
- * constructed at mepol.py:308-311, over n_tensors (<= 8) f64 parameter tensors in one launch.
+ * constructed at mepol.py:308-311, over n_tensors (<= 16) f64 parameter tensors, one launch per 8 of them.
  * exp_avg (Adam only) / exp_avg_sq (Adam; RMSprop square_avg) are updated in place.
  * scalars is DEVICE memory: Adam {enable, lr/bias_correction1, sqrt(bias_correction2), beta1,
  * beta2, eps}; RMSprop {enable, lr, alpha, eps}.  enable == 0 makes the call a no-op. */

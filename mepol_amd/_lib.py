@@ -75,6 +75,9 @@ SIGNATURES = {
     "mepol_policy_forward_masked": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
                                     _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
                                     _c_vp, _c_vp, _c_vp, _c_vp],
+    "mepol_hidden_backward_workspace_size": [_c_i64, _c_int, ctypes.POINTER(_c_sz)],
+    "mepol_hidden_backward": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
+                              _c_sz, _c_vp],
     "mepol_gemm_nt": [_c_vp, _c_i64, _c_int, _c_i64, _c_vp, _c_int, _c_i64, _c_vp, _c_int, _c_vp,
                       _c_i64, _c_int, _c_vp],
     "mepol_step_mountaincar": [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp],

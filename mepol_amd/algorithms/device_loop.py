@@ -21,7 +21,13 @@ before each replay.  After a rejected step the caller restores theta and calls `
 
 Results equal the eager path (autograd through the same kernels) up to the optimizer's
 rounding order; tests/test_gpu_device_loop.py checks both against each other and the oracle.
+
+A ReLU policy with three to six even-width hidden layers runs the same iteration with its own
+network part (MultiLayerIteration: per-layer static activations, gemm_nt forward, a
+hidden_backward chain beside the weight gradients; tests/test_gpu_multilayer_policy.py).
 """
+import contextlib
+import gc
 import math
 import os
 import weakref
@@ -30,7 +36,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..policy import GaussianPolicy
+from ..policy import GaussianPolicy, multilayer_ok
 
 _ADAM, _RMSPROP = 0, 1
 
@@ -76,6 +82,59 @@ def supported(batch, behavioral_policy, target_policy, optimizer):
     if _opt_kind(optimizer) is None:
         return False
     return [id(p) for p in optimizer.param_groups[0]["params"]] == [id(p) for p in params]
+
+
+def supported_multilayer(batch, behavioral_policy, target_policy, optimizer):
+    """supported()'s conditions for the ReLU policies with three to six even-width hidden
+    layers, which MultiLayerIteration runs (policy.multilayer_ok: the shapes _MultiLayerLogp
+    takes).  supported() itself stays False for them: the sharded iteration (parallel.py) asks
+    it and is written for the two-layer parameter list."""
+    if os.environ.get("MEPOL_DEVICE_LOOP", "1") == "0":
+        return False
+    if not isinstance(target_policy, GaussianPolicy) or target_policy is behavioral_policy:
+        return False
+    if not (batch.dense and batch.states_flat.is_cuda):
+        return False
+    if not target_policy._fused_head_ok(batch.states_flat, batch.actions_flat):
+        return False
+    layers = [m for m in target_policy.net if isinstance(m, nn.Linear)]
+    if not multilayer_ok([m.out_features for m in layers], target_policy.num_features):
+        return False
+    params = list(target_policy.parameters())
+    if len(params) != 2 * len(layers) + 3 or any(
+            p.dtype != torch.float64 or not p.is_contiguous() or p.device != batch.device
+            for p in params):
+        return False
+    if _opt_kind(optimizer) is None:
+        return False
+    return [id(p) for p in optimizer.param_groups[0]["params"]] == [id(p) for p in params]
+
+
+_guard_depth, _guard_restore = 0, False
+
+
+@contextlib.contextmanager
+def capture_guard():
+    """Keeps Python's cyclic garbage collector out of a warm-up pass and graph capture.  A
+    collection that starts while a stream is capturing runs the destructors of whatever dead
+    cycles hold (an earlier iteration's graphs, private memory pools, tensors), and the HIP
+    calls those make are not permitted during a capture: the capture is invalidated or, from a
+    destructor, the process aborts.  torch.cuda.graph no longer collects before it begins, so
+    this does (outside the capture, where the destructors are legal) and then holds the
+    collector off until the outermost guard ends; guards nest (two ranks captured in one
+    process)."""
+    global _guard_depth, _guard_restore
+    if _guard_depth == 0:
+        gc.collect()
+        _guard_restore = gc.isenabled()
+        gc.disable()
+    _guard_depth += 1
+    try:
+        yield
+    finally:
+        _guard_depth -= 1
+        if _guard_depth == 0 and _guard_restore:
+            gc.enable()
 
 
 def _scalar_dtype():
@@ -462,8 +521,9 @@ class DeviceIteration:
         self.graphs = graphs
 
     def _capture(self):
-        self._warmup()
-        self._capture_graph()
+        with capture_guard():
+            self._warmup()
+            self._capture_graph()
 
     def _launch(self):
         par = self._next
@@ -521,16 +581,162 @@ class DeviceIteration:
         self.graph = None
 
 
+class MultiLayerIteration(DeviceIteration):
+    """The iteration for a ReLU policy with L >= 3 hidden layers (supported_multilayer): the
+    same replay machinery (scalar blocks, shadows, speculative second graph, cancel); the
+    network part is _MultiLayerLogp's kernel sequence on static per-layer buffers:
+
+        forward   layer_forward -> gemm_nt (bias + ReLU) x (L - 2) -> gemm_nt (z_L) -> head
+        backward  head row kernel -> hidden_backward x (L - 1) -> layer_backward  (one chain)
+                  weight_grad x (L - 1), the head's reduces                       (forked stream)
+
+    dW_l = dz_l^T h_{l-1} needs only dz_l, so every weight gradient runs on the forked stream
+    beside the chain that produces dz_{l-1}, as dW2 runs beside dh1 in the two-layer iteration;
+    the head's parameter-gradient reduces follow the first of them there.  The two-layer
+    iteration's code is left as it is (the sharded iteration builds on it), so the constructor
+    and the body are restated here for the longer parameter list."""
+
+    def __init__(self, target_policy, optimizer, batch, k, G, B, ns, eps):
+        self._tgt_ref, self.opt = weakref.ref(target_policy), optimizer
+        self.kind = _opt_kind(optimizer)
+        self.params = list(target_policy.parameters())  # optimizer / state order
+        layers = [m for m in target_policy.net if isinstance(m, nn.Linear)]
+        L = self.L = len(layers)
+        # (W_1, b_1, ..., W_L, b_L, Wm, bm, log_std): the order _backward returns gradients in
+        self.named = tuple(t for m in layers for t in (m.weight, m.bias)) + (
+            target_policy.mean.weight, target_policy.mean.bias, target_policy.log_std)
+        self.k, self.G, self.B, self.ns, self.eps = k, float(G), float(B), float(ns), float(eps)
+        dev = batch.device
+        self.device = dev
+        N = self.N = batch.N
+        self.nt, self.T, self.kp1 = batch.num_traj, batch.T, batch.kp1
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.x = torch.empty_like(batch.states_flat)
+        self.act = torch.empty_like(batch.actions_flat)
+        self.D = torch.empty_like(batch.D)
+        self.idx32T = torch.empty_like(batch.idx32T)
+        self.offsets = torch.empty_like(batch.offsets)
+        self.logp_b = torch.empty((self.nt, self.T), **f64)
+        off, rows = batch.csr(k)
+        self.csr_off, self.csr_rows = torch.empty_like(off), torch.empty_like(rows)
+        widths = [m.out_features for m in layers]
+        nf, a = self.x.shape[1], target_policy.mean.out_features
+        self.hs = [torch.empty((N, w), **f64) for w in widths[:-1]]   # h_1 .. h_{L-1}
+        self.zL = torch.empty((N, widths[-1]), **f64)
+        # dz_{L-1}, dz_{L-2}, ... alternate between two buffers (dz_L is the head's)
+        self.dz_buf = [torch.empty(N * max(widths[:-1]), **f64) for _ in range(min(2, L - 1))]
+        self.mu = torch.empty((N, a), **f64)
+        self.logp = torch.empty(N, **f64)
+        self.fused_fwd = self.fused_dh1 = False  # the two-layer iteration's fused kernels
+        self.neg_one = torch.full((), -1.0, **f64)
+        self.tracks_shadow = True
+        self.speculative = os.environ.get("MEPOL_SPECULATE", "1") != "0"
+        self._bufs = [self._make_bufs(dev) for _ in range(2 if self.speculative else 1)]
+        self._use(0)
+        self._inflight = []
+        self._next = 0
+        self._last = 0
+        self._events = [torch.cuda.Event() for _ in self._bufs]
+        self.graphs = [None] * len(self._bufs)
+        self.w_cur = torch.zeros(N, **f64)
+        self.g_cur = torch.zeros(N, **f64)
+        self.out_cur = torch.zeros(4, **f64)
+        # one scratch buffer per kernel call site, owned by this graph (never the eager
+        # per-stream cache, whose buffers can be replaced while a graph holds their addresses)
+        self.ws_head = ops.head_workspace(N, widths[-1], a, dev)
+        self.ws_layer = ops.layer_workspace(N, nf, widths[0], dev)
+        self.ws_wgrad = [None] + [ops.weight_grad_workspace(N, widths[l], widths[l - 1], dev)
+                                  for l in range(1, L)]
+        self.ws_hidden = [None] + [ops.hidden_backward_workspace(N, widths[l - 1], dev)
+                                   for l in range(1, L)]
+        self.graph = None
+        self.fork = torch.cuda.Stream(device=dev)
+        self._batch_id = None
+        self._init_state()
+
+    @torch.no_grad()
+    def forward(self):
+        L = self.L
+        Ws, bs = self.named[0:2 * L:2], self.named[1:2 * L:2]
+        Wm, bm, ls = self.named[2 * L:]
+        ops.layer_forward(self.x, Ws[0], bs[0], out=self.hs[0])
+        for l in range(1, L - 1):
+            ops.gemm_nt(self.hs[l - 1], Ws[l], bias=bs[l], relu=True, out=self.hs[l])
+        ops.gemm_nt(self.hs[L - 2], Ws[L - 1], out=self.zL)
+        ops.head_forward(self.zL, Wm, bm, ls, self.act, bz=bs[L - 1], mu_out=self.mu,
+                         logp_out=self.logp)
+
+    def _backward(self, grad):
+        """(dW_1, db_1, ..., dW_L, db_L, dWm, dbm, dls) from dH/dlogp: the _MultiLayerLogp
+        backward.  Index l below is 0-based (Ws[l] = W_{l+1}, hs[l] = h_{l+1})."""
+        L = self.L
+        Ws, bs = self.named[0:2 * L:2], self.named[1:2 * L:2]
+        Wm, _, ls = self.named[2 * L:]
+        cur = torch.cuda.current_stream()
+        self.fork.wait_stream(cur)
+        dzL, dWm, dbm, dls, dbL, head_reduce = ops.head_backward(
+            grad, self.zL, Wm, ls, self.act, self.mu, bz=bs[L - 1], need_dz=True,
+            ws=self.ws_head, defer_reduce=True)
+        dW, db = [None] * L, [None] * L
+        db[L - 1] = dbL
+        dz, dz_slot = dzL, None
+        read_done = {}  # dz buffer -> event after the weight gradient that read it
+        for l in range(L - 1, 0, -1):
+            ready = torch.cuda.Event()
+            ready.record(cur)
+            self.fork.wait_event(ready)
+            with torch.cuda.stream(self.fork):
+                dW[l] = ops.weight_grad(dz, self.hs[l - 1], ws=self.ws_wgrad[l])
+                if l == L - 1:
+                    head_reduce()
+                if dz_slot is not None:
+                    read_done[dz_slot] = torch.cuda.Event()
+                    read_done[dz_slot].record(self.fork)
+            slot = (L - 1 - l) % 2
+            if slot in read_done:  # its previous dz is still being read on the forked stream
+                cur.wait_event(read_done.pop(slot))
+            w = Ws[l].shape[1]
+            out = self.dz_buf[slot][:self.N * w].view(self.N, w)
+            dz, db[l - 1] = ops.hidden_backward(dz, Ws[l], self.hs[l - 1], ws=self.ws_hidden[l],
+                                                dz_out_buf=out)
+            dz_slot = slot
+        dW[0], _ = ops.layer_backward(dz, self.hs[0], self.x, ws=self.ws_layer)
+        cur.wait_stream(self.fork)
+        del dzL, dz  # kept until the forked stream has joined: it read them
+        return tuple(t for pair in zip(dW, db) for t in pair) + (dWm, dbm, dls)
+
+    @torch.no_grad()
+    def _body(self):
+        """DeviceIteration._body with the gradients mapped through the longer self.named."""
+        nt, T, N, k = self.nt, self.T, self.N, self.k
+        lt = self.logp.view(nt, T)
+        self._scal_in()
+        w, g = self.w_cur, self.g_cur
+        gamma, partials, nparts = ops.entropy_gamma(g, w, self.csr_off, self.csr_rows)
+        grad = ops.entropy_reverse_scan(gamma, w, partials, nparts, self.offsets, nt, T,
+                                        self.neg_one)
+        grad_of = {id(p): g for p, g in zip(self.named, self._backward(grad.view(-1)))}
+        self._optim_step([grad_of[id(p)] for p in self.params])
+        self.forward()
+        ops.iw_forward(lt, self.logp_b, self.offsets, N, w_out=self.w_cur)
+        ops.entropy_forward(self.w_cur, self.idx32T, self.D, k, self.ns, self.G, self.B,
+                            self.eps, g_out=self.g_cur, out4=self.out_cur, vals=self.vals)
+        ops.memcpy_async(self.vals_host, self.vals)
+
+
 _CACHE = weakref.WeakKeyDictionary()  # target policy -> DeviceIteration
 
 
 def get(target_policy, optimizer, batch, k, G, B, ns, eps):
-    """The cached DeviceIteration for these arguments (one per target policy)."""
+    """The cached DeviceIteration for these arguments (one per target policy); a
+    MultiLayerIteration for a policy with more than two hidden layers."""
     it = _CACHE.get(target_policy)
     if it is None or not it.matches(target_policy, optimizer, batch, k, G, B, ns, eps):
         it = None  # drop the old graph and buffers before allocating new ones
         _CACHE.pop(target_policy, None)
-        it = DeviceIteration(target_policy, optimizer, batch, k, G, B, ns, eps)
+        deep = sum(isinstance(m, nn.Linear) for m in target_policy.net) > 2
+        cls = MultiLayerIteration if deep else DeviceIteration
+        it = cls(target_policy, optimizer, batch, k, G, B, ns, eps)
         _CACHE[target_policy] = it
     return it
 

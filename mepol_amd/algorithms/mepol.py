@@ -73,8 +73,11 @@ class _RolloutGraph:
         with torch.cuda.stream(side):
             self._body(1)
         torch.cuda.current_stream().wait_stream(side)
+        from .device_loop import capture_guard
+
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+        with capture_guard(), torch.cuda.graph(self.graph, stream=side,
+                                               capture_error_mode="thread_local"):
             self._body(T)
         torch.cuda.current_stream().wait_stream(side)
 
@@ -817,7 +820,9 @@ def off_policy_optimization(optimizer, behavioral_policy, target_policy, last_va
         loop = fns.make_device_loop(optimizer, behavioral_policy, target_policy)
     elif deferred and fns is sys.modules[__name__]:
         batch = P.lookup(states, actions, real_traj_lengths, distances, indices)
-        if device_loop.supported(batch, behavioral_policy, target_policy, optimizer):
+        if (device_loop.supported(batch, behavioral_policy, target_policy, optimizer)
+                or device_loop.supported_multilayer(batch, behavioral_policy, target_policy,
+                                                    optimizer)):
             loop = device_loop.get(target_policy, optimizer, batch, k, G, B, ns, eps)
             if _same_params(target_policy, behavioral_policy):
                 # At an epoch's start the target holds the behavioral parameters (mepol.py:409,

@@ -389,6 +389,90 @@ __global__ __launch_bounds__(l1b::P::kThreads) void dh1_layer1_bwd_kernel(
   }
 }
 
+// ---- backward through a hidden layer (GaussianPolicy.net[2 l], l >= 1, src/policy.py:21-26) ---
+// dz_in = (dz_out W) . relu'(h_in) for W [K][M] as stored (gemm_mainloop's BT form) and the
+// layer's ReLU input h_in [N][M], plus the previous layer's bias gradient db_in[c] = sum_r
+// dz_in[r][c].  The epilogue loads h_in at the accumulator positions, masks and stores dz_in,
+// sums each lane's rows, the four row groups of a wave by two exchanges and the WR waves through
+// LDS in wave order into the row block's record part[rb][M]; sum_records adds the records.
+// Tiling: dh1's 8 waves x (32 rows x 80 cols) with the DEEP main loop.
+namespace hbw {
+constexpr int WR = 8, WC = 1, FR = 2, FC = 5;
+using P = Cfg<WR, WC, FR, FC>;
+constexpr int kGroups = 16;  // sum_records' groups of row blocks
+
+inline int row_blocks(int64_t n) { return (int)((n + P::BM - 1) / P::BM); }
+inline size_t ws_bytes(int64_t n, int m) {
+  return sum_records_bytes<kGroups>(row_blocks(n), (size_t)m);
+}
+
+struct ScatterDb {
+  double* db;
+  __device__ void operator()(int64_t e, double t) const { db[e] = t; }
+};
+}  // namespace hbw
+
+__global__ __launch_bounds__(hbw::P::kThreads) void hidden_bwd_kernel(
+    const double* __restrict__ dz_out, int64_t N, int K, const double* __restrict__ W, int M,
+    const double* __restrict__ h_in, double* __restrict__ dz_in, double* __restrict__ part) {
+  using namespace hbw;
+  constexpr int BM = P::BM, BN = P::BN;
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int fr = frag_col(lane);
+  const int ncb = (M + BN - 1) / BN;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
+  const int rb = tile / ncb;
+  const int64_t row0 = (int64_t)rb * BM;
+  const int col0 = (tile % ncb) * BN;
+  d4 acc[FR][FC];
+  gemm_mainloop<WR, WC, FR, FC, true, true>(dz_out, N, K, K, W, M, M, row0, col0, lds, acc);
+
+  // h_in at every accumulator element in ONE batch of unconditional loads (clamped addresses)
+  // before the first use, as in dh1_layer1_bwd_kernel; rows and columns past the end are
+  // zeroed by the mask below
+  double hv[FC][FR][4];
+#pragma unroll
+  for (int i = 0; i < FR; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t r = row0 + wave * FR * 16 + i * 16 + frag_row(lane, q);
+      const double* hr = h_in + min<int64_t>(r, N - 1) * M;
+#pragma unroll
+      for (int j = 0; j < FC; ++j) hv[j][i][q] = hr[min(col0 + j * 16 + fr, M - 1)];
+    }
+  double* red = lds;  // [WR][BN]; the main loop's last barrier retired its LDS reads
+#pragma unroll
+  for (int j = 0; j < FC; ++j) {
+    const int c = col0 + j * 16 + fr;
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < FR; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t r = row0 + wave * FR * 16 + i * 16 + frag_row(lane, q);
+        const bool in = r < N && c < M;
+        const double v = (in && hv[j][i][q] > 0.0) ? acc[i][j][q] : 0.0;
+        if (in) dz_in[r * M + c] = v;
+        s += v;
+      }
+    // the wave's four row groups (lanes fr, fr + 16, fr + 32, fr + 48): the same bits in all
+    s += __shfl_xor(s, 16, mepol::kWave);
+    s += __shfl_xor(s, 32, mepol::kWave);
+    if (lane < 16) red[wave * BN + j * 16 + fr] = s;
+  }
+  if (part) {  // uniform
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < BN && col0 + t < M) {
+      double s = red[t];
+#pragma unroll
+      for (int w = 1; w < WR; ++w) s += red[w * BN + t];
+      part[(int64_t)rb * M + col0 + t] = s;
+    }
+  }
+}
+
 template <int WR, int WC, int FR, int FC>
 int launch_nt(const double* A, int64_t n, int k, int64_t lda, const double* B, int m,
               int64_t ldb, const double* bias, int relu, double* C, int64_t ldc,
@@ -517,4 +601,48 @@ extern "C" int mepol_dh1_layer1_backward_w2(const double* dz2, int64_t n, int k,
                                             void* stream) {
   return dh1_layer1_backward<true, true>(dz2, n, k, W2, m, h1_mask, x, in_features, dW1, db1,
                                          workspace, workspace_bytes, stream);
+}
+
+
+// Backward through a hidden layer: dz_in [n, in] = (dz_out W) . (h_in > 0) for dz_out [n, out]
+// and W [out, in] as stored, db_in [in] (nullable) = the column sums of dz_in.
+extern "C" int mepol_hidden_backward_workspace_size(int64_t n, int in_features, size_t* bytes) {
+  if (!bytes || n < 0 || in_features <= 0) {
+    mepol::set_error("mepol_hidden_backward_workspace_size: bad arguments (n >= 0, "
+                     "in_features > 0, bytes non-null)");
+    return mepol::kErrBadArg;
+  }
+  *bytes = mepol::gemm::hbw::ws_bytes(n, in_features);
+  return 0;
+}
+
+extern "C" int mepol_hidden_backward(const double* dz_out, int64_t n, int out_features,
+                                     const double* W, const double* h_in, int in_features,
+                                     double* dz_in, double* db_in, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  using namespace mepol::gemm::hbw;
+  const int k = out_features, m = in_features;
+  if (n <= 0 || k <= 0 || m <= 0 || (k & 1) || (m & 1) || !dz_out || !W || !h_in || !dz_in ||
+      !workspace || ((uintptr_t)dz_out & 15) || ((uintptr_t)W & 15)) {
+    mepol::set_error("mepol_hidden_backward: bad arguments (n > 0; out_features and in_features "
+                     "even and positive; dz_out, W, h_in, dz_in and workspace non-null; dz_out "
+                     "and W 16-B aligned)");
+    return mepol::kErrBadArg;
+  }
+  const int nrb = row_blocks(n);
+  const size_t need = ws_bytes(n, m);
+  if (workspace_bytes < need) {
+    mepol::set_error("mepol_hidden_backward: workspace %zu < %zu", workspace_bytes, need);
+    return mepol::kErrWorkspace;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int ncb = (m + P::BN - 1) / P::BN;
+  const unsigned tiles = (unsigned)((int64_t)nrb * ncb);
+  double* part = db_in ? (double*)workspace : nullptr;
+  MEPOL_HIP((mepol::max_dynamic_lds<mepol::gemm::hidden_bwd_kernel>((int)P::kLds)));
+  hipLaunchKernelGGL(mepol::gemm::hidden_bwd_kernel, dim3(tiles), dim3(P::kThreads), P::kLds, st,
+                     dz_out, n, k, W, m, h_in, dz_in, part);
+  MEPOL_CHECK_LAUNCH();
+  if (!db_in) return 0;
+  return mepol::sum_records<kGroups>(part, nrb, (int64_t)m, ScatterDb{db_in}, st);
 }

@@ -21,7 +21,8 @@
 namespace mepol {
 namespace optim {
 
-constexpr int kMaxTensors = 8;
+constexpr int kMaxTensors = 8;       // tensors per launch
+constexpr int kMaxCallTensors = 16;  // per call (six hidden layers: 2 * 6 + 3); launches of <= 8
 
 struct Tensors {
   double* p[kMaxTensors];
@@ -97,19 +98,32 @@ extern "C" int mepol_optim_step_snapshot(int kind, int n_tensors, double* const*
                                          const double* scalars, double* const* params_snap,
                                          double* const* exp_avg_snap,
                                          double* const* exp_avg_sq_snap, void* stream) {
-  if ((kind != 0 && kind != 1) || n_tensors <= 0 || n_tensors > kMaxTensors || !params || !grads ||
-      !exp_avg_sq || !sizes || !scalars || (kind == 0 && !exp_avg)) {
+  if ((kind != 0 && kind != 1) || n_tensors <= 0 || n_tensors > kMaxCallTensors || !params ||
+      !grads || !exp_avg_sq || !sizes || !scalars || (kind == 0 && !exp_avg)) {
     set_error("mepol_optim_step: bad arguments (kind 0=Adam/1=RMSprop, 1..%d tensors)",
-              kMaxTensors);
+              kMaxCallTensors);
     return kErrBadArg;
   }
-  Tensors t{};
-  int64_t nmax = 1;
   for (int i = 0; i < n_tensors; ++i) {
     if (!params[i] || !grads[i] || !exp_avg_sq[i] || (kind == 0 && !exp_avg[i]) || sizes[i] < 0) {
       set_error("mepol_optim_step: null tensor %d", i);
       return kErrBadArg;
     }
+  }
+  if (n_tensors > kMaxTensors) {  // one launch per kMaxTensors tensors, each as a call of its own
+    for (int i0 = 0; i0 < n_tensors; i0 += kMaxTensors) {
+      const int rc = mepol_optim_step_snapshot(
+          kind, std::min(kMaxTensors, n_tensors - i0), params + i0, grads + i0,
+          exp_avg ? exp_avg + i0 : nullptr, exp_avg_sq + i0, sizes + i0, scalars,
+          params_snap ? params_snap + i0 : nullptr, exp_avg_snap ? exp_avg_snap + i0 : nullptr,
+          exp_avg_sq_snap ? exp_avg_sq_snap + i0 : nullptr, stream);
+      if (rc != 0) return rc;
+    }
+    return 0;
+  }
+  Tensors t{};
+  int64_t nmax = 1;
+  for (int i = 0; i < n_tensors; ++i) {
     t.p[i] = params[i];
     t.g[i] = grads[i];
     t.m[i] = kind == 0 ? exp_avg[i] : nullptr;

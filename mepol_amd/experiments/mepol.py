@@ -65,6 +65,9 @@ def build_parser():
                    help="The tensorboard directory under which the directory of this experiment is put")
     p.add_argument("--results_dir", type=str, default=None,
                    help="(build extension) root of results/exploration; default: ./results/exploration")
+    p.add_argument("--hidden_sizes", type=int, nargs="+", default=None, metavar="N",
+                   help="(build extension) hidden layer widths of the policy instead of the "
+                        "experiment spec's; default: the spec's")
     return p
 
 
@@ -143,9 +146,13 @@ def main(argv=None):
     env = spec["env_create"]()
     state_filter = spec.get("state_filter")
     eps = spec["eps"]
+    hidden_sizes = args.hidden_sizes if args.hidden_sizes is not None else spec["hidden_sizes"]
+    if any(w <= 0 for w in hidden_sizes):
+        print("--hidden_sizes needs positive widths.")
+        return 4
 
     def create_policy(is_behavioral=False):
-        policy = GaussianPolicy(num_features=env.num_features, hidden_sizes=spec["hidden_sizes"],
+        policy = GaussianPolicy(num_features=env.num_features, hidden_sizes=hidden_sizes,
                                 action_dim=env.action_space.shape[0],
                                 activation=spec["activation"],
                                 log_std_init=spec["log_std_init"]).to(device)
@@ -160,6 +167,8 @@ def main(argv=None):
                 f"fe_traj_sc={args.full_entropy_traj_scale},fe_k={args.full_entropy_k},"
                 f"use_bt={args.use_backtracking},bt_coeff={args.backtrack_coeff},"
                 f"max_bt_try={args.max_backtrack_try}")
+    if args.hidden_sizes is not None:
+        exp_name += ",hidden=" + "x".join(str(w) for w in args.hidden_sizes)
     root = args.results_dir or os.path.join(os.getcwd(), "results", "exploration")
     out_path = os.path.join(root, args.tb_dir_name, exp_name + "__" +
                             datetime.now().strftime("%Y_%m_%d_%H_%M_%S") + "__" + str(os.getpid()))
@@ -169,6 +178,8 @@ def main(argv=None):
         f.write("Run info:\n")
         f.write("-" * 10 + "\n")
         for key, value in vars(args).items():
+            if key == "hidden_sizes" and value is None:
+                continue  # absent: the file is the one a run without the flag always wrote
             f.write(f"{key}={value}\n")
         f.write("-" * 10 + "\n")
         f.write(str(create_policy()))

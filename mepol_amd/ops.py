@@ -487,6 +487,33 @@ def weight_grad(dy, x, out=None, ws=None):
     return dW
 
 
+def hidden_backward_workspace(n, in_features, device):
+    """Scratch of hidden_backward (its row blocks' column sums), owned by the caller."""
+    return _own_workspace(device, "hidden_backward", n, in_features)
+
+
+def hidden_backward(dz_out, W, h_in, ws=None, dz_out_buf=None, db_out=None):
+    """(dz_in, db_in) of a hidden layer h_out = relu(h_in W^T + b) from dz_out = dL/d(its
+    pre-activation) [n, out]: dz_in = (dz_out W) * (h_in > 0) [n, in], the gradient at the
+    previous layer's pre-activation, and db_in = dz_in.sum(0), that layer's bias gradient
+    (csrc/gemm.hip: W read as stored on the f64 matrix cores, fixed-order column sums).
+    `dz_out_buf` / `db_out`: optional tensors the results are written into."""
+    n, o = dz_out.shape
+    i = W.shape[1]
+    assert W.shape[0] == o and h_in.shape == (n, i)
+    assert dz_out.is_contiguous() and W.is_contiguous() and h_in.is_contiguous()
+    assert dz_out.dtype == torch.float64 and W.dtype == torch.float64 and h_in.dtype == torch.float64
+    ws = _ws_or_cached(ws, dz_out.device, "hidbwd", "hidden_backward", n, i)
+    dz = dz_out_buf if dz_out_buf is not None else torch.empty((n, i), dtype=torch.float64,
+                                                                device=dz_out.device)
+    db = db_out if db_out is not None else torch.empty(i, dtype=torch.float64,
+                                                       device=dz_out.device)
+    assert dz.is_contiguous() and dz.shape == (n, i) and db.is_contiguous() and db.numel() == i
+    call("mepol_hidden_backward", ptr(dz_out), n, o, ptr(W), ptr(h_in), i, ptr(dz), ptr(db),
+         ptr(ws), ws.numel(), _stream())
+    return dz, db
+
+
 def gemm_nt(A, B, bias=None, relu=False, out=None, variant=0):
     """act(A B^T + bias) on the f64 matrix cores: A [n, k], B [m, k] (row-major, k even)."""
     n, k = A.shape

@@ -27,7 +27,7 @@ import weakref
 import torch
 
 from . import ops as _hip_ops
-from .algorithms.device_loop import DeviceIteration
+from .algorithms.device_loop import DeviceIteration, capture_guard
 
 
 def prepare_nccl_env():
@@ -500,17 +500,18 @@ class ShardedIteration(DeviceIteration):
         rank (raised), not a reason to fall back, because the other ranks would otherwise wait
         in a collective it never joins.  Only the capture itself -- collectives are recorded,
         not executed -- may fail over to the eager path, by consensus (MIN of a flag)."""
-        self._warmup()
         ok = 1
-        try:
-            self._capture_graph()
-        except Exception as e:  # capture unsupported here: every rank falls back together
-            import warnings
+        with capture_guard():  # no cyclic garbage collection inside the warm-up or the capture
+            self._warmup()
+            try:
+                self._capture_graph()
+            except Exception as e:  # capture unsupported here: every rank falls back together
+                import warnings
 
-            warnings.warn(f"sharded iteration capture failed, running eagerly: {e!r}")
-            self.graph = None
-            ok = 0
-            torch.cuda.synchronize()
+                warnings.warn(f"sharded iteration capture failed, running eagerly: {e!r}")
+                self.graph = None
+                ok = 0
+                torch.cuda.synchronize()
         flag = torch.tensor([ok], dtype=torch.int32, device=self.device)
         self.dist.all_reduce(flag, op=self.dist.ReduceOp.MIN, group=self.group)
         if int(flag.item()) == 0:

@@ -8,7 +8,11 @@ Parameters are float64 (the reference's dtype, src/utils/dtypes.py:3) and are in
 the CPU generator in the reference's order (Linear defaults, then xavier_uniform on
 ``mean.weight`` and the ``net`` weights, policy.py:36-41), so a given torch seed yields the
 reference's initial weights; the module can then be moved to the GPU with ``.to(device)``.
-The forward/backward runs on PyTorch-ROCm (hipBLASLt/rocBLAS GEMMs).
+Large f64 batches of a ReLU policy take the library's HIP kernels end to end: two hidden
+layers through _TwoLayerLogp, three to six even-width hidden layers through _MultiLayerLogp
+(f64 matrix-core GEMMs, csrc/gemm.hip, csrc/wgrad.hip; fused head, csrc/head.hip).  Every other
+shape (one hidden layer, odd widths, other activations, small batches) runs its Linear layers
+on PyTorch-ROCm (hipBLASLt/rocBLAS GEMMs).
 """
 import math
 
@@ -132,6 +136,65 @@ class _TwoLayerLogp(torch.autograd.Function):
         return None, dW1, db1, dW2, db2, dWm, dbm, dls, None
 
 
+MULTILAYER_MIN, MULTILAYER_MAX = 3, 6  # hidden layers of _MultiLayerLogp (2 L + 3 <= 16 tensors)
+
+
+def multilayer_ok(widths, num_features):
+    """True for the hidden widths _MultiLayerLogp takes: 3 to 6 layers, all even (16-B aligned
+    weight rows for the matrix-core kernels), behind an input layer of at most 64 features."""
+    return (MULTILAYER_MIN <= len(widths) <= MULTILAYER_MAX and num_features <= 64
+            and all(w % 2 == 0 for w in widths))
+
+
+class _MultiLayerLogp(torch.autograd.Function):
+    """log p(a | s) of a ReLU policy with L >= 3 hidden layers for a large batch, from the
+    library's kernels only (args: x, actions, W_1, b_1, ..., W_L, b_L, Wm, bm, log_std):
+
+    layer 1        h_1 = relu(x W_1^T + b_1)             csrc/mlp.hip
+    layers 2..L-1  h_l = relu(h_{l-1} W_l^T + b_l)       f64 MFMA GEMM (csrc/gemm.hip)
+    layer L        z_L = h_{L-1} W_L^T                    the same GEMM without bias / ReLU
+    head           logp(relu(z_L + b_L) Wm^T + bm)        csrc/head.hip, b_L + ReLU folded in
+    backward: head (dz_L, dWm, dbm, dlog_std, db_L), then for l = L .. 2 the split-K
+    dW_l = dz_l^T h_{l-1} (csrc/wgrad.hip) and (dz_{l-1}, db_{l-1}) = hidden_backward(dz_l, W_l,
+    h_{l-1}) (csrc/gemm.hip), then layer 1's dW_1 from dz_1 (its ReLU mask is idempotent on the
+    already masked dz_1).  Same math as nn.Linear/ReLU."""
+
+    @staticmethod
+    def forward(ctx, x, actions, *params):
+        from . import ops
+
+        L = (len(params) - 3) // 2
+        Ws, bs = params[0:2 * L:2], params[1:2 * L:2]
+        Wm, bm, log_std = params[2 * L:]
+        hs = [ops.layer_forward(x, Ws[0], bs[0])]
+        for l in range(1, L - 1):
+            hs.append(ops.gemm_nt(hs[-1], Ws[l], bias=bs[l], relu=True))
+        zL = ops.gemm_nt(hs[-1], Ws[L - 1])
+        mu, logp = ops.head_forward(zL, Wm, bm, log_std, actions, bz=bs[L - 1])
+        ctx.L = L
+        ctx.save_for_backward(x, actions, zL, mu, Wm, log_std, bs[L - 1], *Ws[1:], *hs)
+        return logp
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+
+        L = ctx.L
+        x, actions, zL, mu, Wm, log_std, bL = ctx.saved_tensors[:7]
+        Ws = (None,) + ctx.saved_tensors[7:7 + L - 1]   # Ws[l] = W_{l+1}, l >= 1
+        hs = ctx.saved_tensors[7 + L - 1:]              # hs[l] = h_{l+1}
+        dz, dWm, dbm, dls, dbL = ops.head_backward(g.contiguous(), zL, Wm, log_std, actions, mu,
+                                                   bz=bL, need_dz=True)
+        dW, db = [None] * L, [None] * L
+        db[L - 1] = dbL
+        for l in range(L - 1, 0, -1):
+            dW[l] = ops.weight_grad(dz, hs[l - 1])
+            dz, db[l - 1] = ops.hidden_backward(dz, Ws[l], hs[l - 1])
+        dW[0], _ = ops.layer_backward(dz, hs[0], x)
+        grads = [t for pair in zip(dW, db) for t in pair]
+        return (None, None, *grads, dWm, dbm, dls)
+
+
 def _apply_linear(layer, x):
     if x.dim() == 2 and x.shape[0] >= SPLITK_MIN_ROWS and torch.is_grad_enabled():
         return _Linear.apply(x, layer.weight, layer.bias)
@@ -186,6 +249,11 @@ class GaussianPolicy(nn.Module):
                 return _TwoLayerLogp.apply(states.contiguous(), l1.weight.contiguous(), l1.bias,
                                            l2.weight, l2.bias, self.mean.weight.contiguous(),
                                            self.mean.bias, self.log_std, actions.contiguous())
+            if multilayer_ok([m.out_features for m in layers], self.num_features):
+                flat = [t for m in layers for t in (m.weight.contiguous(), m.bias)]
+                return _MultiLayerLogp.apply(states.contiguous(), actions.contiguous(), *flat,
+                                             self.mean.weight.contiguous(), self.mean.bias,
+                                             self.log_std)
             h = states
             for layer in layers[:-1]:
                 h = torch.relu(_apply_linear(layer, h))

@@ -354,12 +354,15 @@ class DeviceIteration:
         `outs`: optional tensors of those seven shapes the kernels write into (the sharded
         iteration passes views of its flat all-reduce buffer: no concatenation launch).
         `after_dW2`: optional callable issued on the dW2 stream once dW2 and the head gradients
-        are written, concurrent with the dh1 / layer-1 backward (the sharded iteration starts
-        that bucket's all-reduce there).
+        are written, while the dh1 / layer-1 backward runs (the sharded iteration starts that
+        bucket's all-reduce there).
 
-        Head backward, then dW2 (split-K f64 MFMA, csrc/wgrad.hip, forked stream) concurrent with the fused
-        dh1 -> layer-1 backward (measured: faster than dh1 first with dW2 overlapping the
-        layer-1 backward, and than splitting dW2 across both phases)."""
+        Head backward, then dW2 (split-K f64 MFMA, csrc/wgrad.hip) on a forked stream next to the
+        fused dh1 -> layer-1 backward.  At C3 the two run in series, not concurrently: dW2's
+        ~2000 one-wave workgroups at 256 VGPRs take every wave slot in one round, and a dh1
+        workgroup (8 waves, 84 KB of LDS) becomes resident only as they retire, so dW2's time
+        comes off the iteration one for one (measured: this order is faster than dh1 first with
+        dW2 next to the layer-1 backward, and than splitting dW2 across both phases)."""
         W1, b1, W2, b2, Wm, bm, ls = self.named
         cur = torch.cuda.current_stream()
         # W2^T for the fused dh1 kernel when it cannot read W2 as stored (round 6: with the

@@ -32,7 +32,13 @@ __device__ __forceinline__ int xcd_tile(int L, int ntiles) {
 //   zero_tail(slot, s)  zero what the ragged stage s read past the end of K
 //   mul(slot)           the MFMAs of a slot
 // Slot numbers are compile-time after unrolling, so the ring stays in registers.
-template <int NS, typename I, typename Load, typename ZeroTail, typename Mul>
+// PIN: scheduling barriers hold the compiled code to this issue order -- the loads of stage
+// s + NS - 1, then the MFMAs of stage s, which wait only for loads a whole MFMA block old.
+// Without them the scheduler is free to sink a slot's loads below the MFMAs that should cover
+// them (it did in wgrad_kernel: both slots' loads back to back after the first MFMA block, so
+// every second stage started with no lookahead).  The caller chooses: a kernel whose free
+// schedule already interleaves the loads with the previous MFMAs is better left unpinned.
+template <int NS, bool PIN, typename I, typename Load, typename ZeroTail, typename Mul>
 __device__ __forceinline__ void ring_k_loop(I nfull, I nst, Load load, ZeroTail zero_tail,
                                             Mul mul) {
 #pragma unroll
@@ -44,7 +50,9 @@ __device__ __forceinline__ void ring_k_loop(I nfull, I nst, Load load, ZeroTail 
 #pragma unroll
     for (int p = 0; p < NS; ++p) {
       load((p + NS - 1) % NS, min(s + p + NS - 1, nst - 1));
+      if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
       mul(p);
+      if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
     }
   }
   // the remaining (< NS) full stages and the ragged last one, in the same ring rotation
@@ -53,7 +61,9 @@ __device__ __forceinline__ void ring_k_loop(I nfull, I nst, Load load, ZeroTail 
     if (s + p < nst) {  // uniform
       if (s + p + NS - 1 < nst) load((p + NS - 1) % NS, s + p + NS - 1);
       if (s + p >= nfull) zero_tail(p, s + p);
+      if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
       mul(p);
+      if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
     }
   }
 }

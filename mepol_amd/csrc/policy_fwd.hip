@@ -359,7 +359,9 @@ __global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(2))
       for (int u = 0; u < FI; ++u)
         acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(D[t].y, D[FO + u].y, acc[t][u], 0, 0, 0);
   };
-  mfma::ring_k_loop<NS>(
+  // not pinned: left to the scheduler, this loop's loads are interleaved with the previous
+  // stage's MFMAs and wait for the older batch only; pinned it measured the same (889 us at C3)
+  mfma::ring_k_loop<NS, false>(
       nfull, nst, [&](int p, int st) __attribute__((always_inline)) { load(R[p], st); },
       [&](int p, int st) __attribute__((always_inline)) {
         if (8 * st + 2 * g >= H1) {  // the tail stage's missing pairs

@@ -36,6 +36,11 @@ constexpr int NL = FO + FI;        // operand loads per lane and k-step
 // (tools/wgrad_probe.py, profiles/r5/f64/wgrad_probe.txt): 64 x 64 tiles with 3 stages, and
 // 80 x 80 tiles at one wave per SIMD with 2 or 3 stages.
 constexpr int NS = 2;
+// ring_k_loop's issue order is pinned: left to the scheduler, both slots' loads were issued back
+// to back after the first MFMA block, and every second k-step began with no load lookahead.
+// Pinned (profiles/r7/kloop/): 891 -> 800 us at C3.  A third stage (it fits in 235 VGPRs with
+// the row addresses as a uniform base plus 32-bit lane offsets) measured no faster than two.
+constexpr bool kPin = true;
 constexpr int kMaxSlices = 128;
 constexpr int kSliceRowsMin = 256;
 
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kOcc))) void
   const int64_t rows = r_end - r_begin;
   const int64_t nfull = rows / 4;  // k-steps with 4 rows in the slice
   const int64_t nks = (rows + 3) / 4;
-  mfma::ring_k_loop<NS>(
+  mfma::ring_k_loop<NS, kPin>(
       nfull, nks, [&](int p, int64_t ks) __attribute__((always_inline)) { load(R[p], ks); },
       [&](int p, int64_t ks) __attribute__((always_inline)) {
         const bool ok = r_begin + 4 * ks + g < r_end;  // rows past the slice end contribute zero

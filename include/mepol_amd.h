@@ -184,6 +184,31 @@ int mepol_rollout_mlp_workspace_size(int64_t n, int64_t T, int h0, int h1, int a
 int mepol_rollout_mlp_plan_info(int64_t n, int h0, int h1, int a_dim, int* workgroups_per_traj,
                                 int* k_chunks);
 
+/* The same rollout for a ReLU policy with 3 <= n_hidden <= 6 hidden layers, nf = 2 ->
+ * [h_1 .. h_L] -> a_dim, every width in 1 .. 512 (odd widths included), a_dim <= 8 (GridWorld: 2),
+ * in one launch with one workgroup per trajectory.  widths is a HOST array of n_hidden ints.
+ * W1 [h_1,2], b1 [h_1]; Wt holds W_2^T .. W_L^T back to back, layer l as [h_{l-1}][h_l]; bt holds
+ * b_2 .. b_L back to back; Wm [a_dim,h_L], bm, log_std [a_dim].  init64 / init32, noise,
+ * states_rec, actions_rec, visited and final_state as for mepol_rollout_mlp.  The workspace
+ * (nullable) is the 256-byte error-word header, zeroed by every call; no form of this kernel
+ * sets the word (its workgroups exchange nothing).  n <= 0 or T <= 0 returns 0 without a launch;
+ * every other argument is validated on the host before any launch (MEPOL_ERR_BAD_ARG).
+ * Summation order, the same contract as mepol_rollout_mlp's: layer 1 is
+ * relu((x0 w0 + x1 w1) + b); column j of layer l >= 2 is four fma chains over the k ranges
+ * [r Lc, min(r Lc + Lc, h_{l-1})), Lc = ceil(h_{l-1} / 4), each from 0.0 in k order, combined as
+ * ((c0 + c1) + c2) + c3, then + b, then ReLU; the mean layer sums Wm[a][j] h_L[j] per 64 columns
+ * by the xor butterfly 32 .. 1, adds those sums in order, then bm[a]. */
+int mepol_rollout_deep(int env_id, int n_hidden, const int* widths, const double* W1,
+                       const double* b1, const double* Wt, const double* bt, const double* Wm,
+                       const double* bm, const double* log_std, int a_dim, const double* init64,
+                       const float* init32, const double* noise, int64_t n, int64_t T,
+                       float* states_rec, float* actions_rec, double* visited,
+                       double* final_state, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* Workspace of mepol_rollout_deep at these sizes: 256 bytes (the error-word header). */
+int mepol_rollout_deep_workspace_size(int64_t n, int64_t T, int n_hidden, const int* widths,
+                                      int a_dim, size_t* bytes);
+
 /* ---- policy MLP (GaussianPolicy, src/policy.py:16-51) for the large-batch passes -----------
  * Gaussian head: mean layer + log-probability with the last hidden layer's bias and ReLU folded
  * in.  z [n, hidden] is the last hidden layer's PRE-activation WITHOUT its bias bz (nullable);

@@ -91,6 +91,11 @@ SIGNATURES = {
                                          ctypes.POINTER(_c_sz)],
     "mepol_rollout_mlp_plan_info": [_c_i64, _c_int, _c_int, _c_int, ctypes.POINTER(_c_int),
                                     ctypes.POINTER(_c_int)],
+    "mepol_rollout_deep": [_c_int, _c_int, ctypes.POINTER(_c_int), _c_vp, _c_vp, _c_vp, _c_vp,
+                           _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp,
+                           _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp],
+    "mepol_rollout_deep_workspace_size": [_c_i64, _c_i64, _c_int, ctypes.POINTER(_c_int), _c_int,
+                                          ctypes.POINTER(_c_sz)],
     "mepol_memcpy_async": [_c_vp, _c_vp, _c_sz, _c_vp],
     "mepol_optim_step": [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],
     "mepol_optim_step_snapshot": [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,

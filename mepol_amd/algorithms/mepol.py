@@ -153,6 +153,34 @@ def _rollout_mlp_layers(policy, nf, a_dim):
     return tuple((m.weight.detach(), m.bias.detach()) for m in layers)
 
 
+# Weight words of layers 2 .. L (sum of h_{l-1} h_l) up to which the deep rollout kernel beat the
+# replayed per-step graph: it streams them from L2 every step, at 2 * 512^2 words ([512] x 3) it
+# still won (60.4 against 62.7 us per step) and at every larger measured shape it lost (DESIGN.md
+# section 3, Rollout).  MEPOL_ROLLOUT_DEEP_MAX_WORDS overrides it (tools/rollout_deep_bench.py).
+ROLLOUT_DEEP_MAX_WORDS = 2 * 512 * 512
+
+
+def _rollout_deep_layers(policy, nf, a_dim):
+    """[(W1, b1), ..., (W_L, b_L)] when the policy is an nf = 2 -> [h_1 .. h_L] -> a ReLU MLP in
+    f64 with 3 to 6 hidden layers that the deep one-launch rollout kernel covers (h <= 512, odd
+    widths included, a <= 8; csrc/rollout_deep.hip) and is measured to be faster for (at most
+    ROLLOUT_DEEP_MAX_WORDS weight words behind layer 1); else None.  Two hidden layers are
+    _rollout_mlp_layers'."""
+    if os.environ.get("MEPOL_ROLLOUT_FUSED", "1") == "0" or nf != 2 or a_dim > 8:
+        return None
+    if getattr(policy, "activation", None) is not nn.ReLU:
+        return None
+    layers = [m for m in policy.net if isinstance(m, nn.Linear)]
+    if not 3 <= len(layers) <= 6 or any(m.weight.dtype != torch.float64 for m in layers):
+        return None
+    if layers[0].in_features != 2 or max(m.out_features for m in layers) > 512:
+        return None
+    cap = int(os.environ.get("MEPOL_ROLLOUT_DEEP_MAX_WORDS", ROLLOUT_DEEP_MAX_WORDS))
+    if sum(m.in_features * m.out_features for m in layers[1:]) > cap:
+        return None
+    return [(m.weight.detach(), m.bias.detach()) for m in layers]
+
+
 def collect_particles_device(env, policy, num_traj, traj_len, state_filter, generator=None,
                              visited=None, shard=None):
     """Rollout of num_traj trajectories of traj_len steps, batched on the policy's device.
@@ -193,11 +221,18 @@ def collect_particles_device(env, policy, num_traj, traj_len, state_filter, gene
             noise_all = torch.randn((T, total, a_dim), dtype=torch.float64, device=dev,
                                     generator=generator)
             lin = _rollout_mlp_layers(policy, nf, a_dim)
-            if lin is not None:  # all T steps in one launch (csrc/envs.hip rollout_mlp_kernel)
-                (W1, b1), (W2, b2) = lin
-                ops.rollout_mlp(env_id, W1, b1, W2, b2, policy.mean.weight.detach(),
-                                policy.mean.bias.detach(), policy.log_std.detach(), init,
-                                noise_all[:, lo:hi], states, actions, visited)
+            deep = _rollout_deep_layers(policy, nf, a_dim) if lin is None else None
+            if lin is not None or deep is not None:
+                # all T steps in one launch (csrc/envs.hip rollout_mlp_kernel, or
+                # csrc/rollout_deep.hip for 3 to 6 hidden layers)
+                head = (policy.mean.weight.detach(), policy.mean.bias.detach(),
+                        policy.log_std.detach(), init, noise_all[:, lo:hi], states, actions,
+                        visited)
+                if lin is not None:
+                    (W1, b1), (W2, b2) = lin
+                    ops.rollout_mlp(env_id, W1, b1, W2, b2, *head)
+                else:
+                    ops.rollout_deep(env_id, deep, *head)
                 rtl = torch.full((num_traj, 1), T, dtype=torch.int32, device=dev)
                 next_states = states[:, 1:, :].reshape(-1, nf)
                 if state_filter is not None:

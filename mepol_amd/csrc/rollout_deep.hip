@@ -1,0 +1,313 @@
+// Whole rollout in one launch for ReLU policies with 3 to 6 hidden layers (mepol_rollout_deep):
+// all T steps of collect_particles (mepol.py:81-90) for nf = 2 -> [h_1 .. h_L] -> a_dim in f64
+// on MountainCar / GridWorld.  One workgroup per trajectory, as rollout_mlp_kernel (envs.hip):
+// thread j owns column j of every layer.  Layer 1 (nf = 2) runs from registers; the hidden
+// activations ping-pong between two LDS vectors; the transposed weights W_l^T ([h_{l-1}][h_l],
+// k-major) of layers 2 .. L are read coalesced from L2 every step (one 8-byte word per thread
+// per k), except the leading rows of the packed W_2^T .. W_L^T buffer that fit in dynamic LDS
+// (MEPOL_ROLLOUT_KL caps their number) and stay there for all T steps.  Thread 0 forms the
+// action, steps the env and records, with the next step's noise loaded a step ahead.  Only
+// __syncthreads(): L + 1 barriers per step, no exchange between workgroups.
+//
+// Summation order (the contract shards and any later form rely on; the two-layer kernels
+// document the same one):
+//   layer 1       relu((x0 w0 + x1 w1) + b), explicit _rn operations;
+//   layer l >= 2  column j: four fma chains over the k ranges [r Lc, min(r Lc + Lc, h_{l-1})),
+//                 Lc = ceil(h_{l-1} / 4), each from 0.0 in k order (an empty range is 0.0),
+//                 combined as ((c0 + c1) + c2) + c3, then + b, then ReLU;
+//   mean layer    per 64-column wave the products Wm[a][j] h_L[j] summed by the xor butterfly
+//                 32, 16, .. 1 (columns past h_L are 0.0), the waves added in order, then + bm[a];
+//   action        mu + noise * exp(log_std), explicit _rn operations.
+#include <algorithm>
+#include <climits>
+#include <cstdlib>
+
+#include "common.hpp"
+#include "env_step.hpp"
+
+namespace mepol {
+namespace envs {
+
+constexpr int kDeepMaxH = 512;   // kRollMaxH of envs.hip
+constexpr int kDeepMaxA = 8;
+constexpr int kDeepMinL = 3, kDeepMaxL = 6;
+constexpr int kDeepChunks = 4;
+constexpr int kDeepU = 8;  // streamed W^T rows per batch of loads
+constexpr int kDeepLdsBytes = 150 * 1024;  // dynamic LDS for resident W^T rows (as rollout_mlp)
+
+struct DeepShape {
+  int L;                // hidden layers
+  int h[kDeepMaxL];     // their widths
+  int kl[kDeepMaxL];    // kl[l], l >= 1: leading rows of layer l + 1's W^T resident in LDS
+};
+
+// Column j of one hidden layer: sum_r c_r over the kDeepChunks row ranges of W^T [hp][hl].  Rows
+// below KL come from LDS (sw, [KL][hl]), the rest stream from L2 (col = W^T + j) in batches of
+// U loads with the next batch in flight while this one is summed, as rollout_mlp_kernel does.
+// (Taking the four ranges as one stream of loads that runs ahead across the range boundaries was
+// slower, 33.6 us per step at [300, 300, 300] against 28.0 with U = 8 and 36.4 with U = 16:
+// DESIGN.md section 3, Rollout.)
+template <int U>
+__device__ __forceinline__ double deep_column(const double* __restrict__ sw,
+                                              const double* __restrict__ col,
+                                              const double* __restrict__ hin, int hp, int hl,
+                                              int KL, int j) {
+  const int Lc = (hp + kDeepChunks - 1) / kDeepChunks;
+  double acc = 0.0;
+  for (int r = 0; r < kDeepChunks; ++r) {
+    const int ka = min(r * Lc, hp), kb = min(ka + Lc, hp);
+    double c = 0.0;
+    int k = ka;
+    for (; k < min(kb, KL); ++k) c = fma(sw[k * hl + j], hin[k], c);
+    double cur[U], nxt[U];
+    const int kend = k + ((kb - k) / U) * U;
+    if (k < kend) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) cur[u] = col[(int64_t)(k + u) * hl];
+      for (; k < kend; k += U) {
+        if (k + U < kend) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) nxt[u] = col[(int64_t)(k + U + u) * hl];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) c = fma(cur[u], hin[k + u], c);
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+      }
+    }
+    for (; k < kb; ++k) c = fma(col[(int64_t)k * hl], hin[k], c);
+    acc = r == 0 ? c : acc + c;
+  }
+  return acc;
+}
+
+template <int ENV>
+__global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
+    const double* __restrict__ W1, const double* __restrict__ b1, const double* __restrict__ Wt,
+    const double* __restrict__ bt, const double* __restrict__ Wm, const double* __restrict__ bm,
+    const double* __restrict__ log_std, int a_dim, const double* __restrict__ init64,
+    const float* __restrict__ init32, const double* __restrict__ noise, int64_t n, int64_t T,
+    float* __restrict__ states_rec, float* __restrict__ actions_rec,
+    double* __restrict__ visited, double* __restrict__ final_state, DeepShape sh) {
+  extern __shared__ double sW[];  // resident rows of W_2^T .. W_L^T, layer after layer
+  __shared__ double sx[2];
+  __shared__ double shid[2][kDeepMaxH];  // hidden activations, ping-pong
+  __shared__ double spart[kDeepMaxH / 64][kDeepMaxA];
+  const int64_t i = blockIdx.x;
+  const int j = threadIdx.x, lane = j & 63, wave = j >> 6;
+  const int L = sh.L;
+  const bool c0 = j < sh.h[0];
+  const double w1a = c0 ? W1[2 * j] : 0.0, w1b = c0 ? W1[2 * j + 1] : 0.0;
+  const double bb1 = c0 ? b1[j] : 0.0;
+  // the resident rows of layers 2 .. L into LDS
+  {
+    int64_t woff = 0;
+    int soff = 0;
+    for (int l = 1; l < L; ++l) {
+      const int words = sh.kl[l] * sh.h[l];
+      for (int w = j; w < words; w += blockDim.x) sW[soff + w] = Wt[woff + w];
+      woff += (int64_t)sh.h[l - 1] * sh.h[l];
+      soff += words;
+    }
+  }
+  const int hL = sh.h[L - 1];
+  const bool cL = j < hL;
+  double wm[kDeepMaxA];
+#pragma unroll
+  for (int a = 0; a < kDeepMaxA; ++a) wm[a] = (cL && a < a_dim) ? Wm[a * hL + j] : 0.0;
+  const int nwL = (hL + 63) >> 6;  // waves that hold columns of the last hidden layer
+  double p = 0.0, v = 0.0;  // MountainCar state (thread 0)
+  float gx = 0.f, gy = 0.f;  // GridWorld state (thread 0)
+  if (j == 0) {
+    if (ENV == 0) {
+      p = init64[2 * i];
+      v = init64[2 * i + 1];
+      sx[0] = p;
+      sx[1] = v;
+    } else {
+      gx = init32[2 * i];
+      gy = init32[2 * i + 1];
+      sx[0] = (double)gx;
+      sx[1] = (double)gy;
+    }
+    states_rec[(i * (T + 1)) * 2 + 0] = (float)sx[0];
+    states_rec[(i * (T + 1)) * 2 + 1] = (float)sx[1];
+  }
+  // thread 0: exp(log_std) once, and the next step's noise loaded a step ahead (its global
+  // latency would otherwise sit on the serial tail of every step)
+  double sd[kDeepMaxA], nz[kDeepMaxA];
+  if (j == 0) {
+    for (int a = 0; a < a_dim; ++a) {
+      sd[a] = exp(log_std[a]);
+      nz[a] = noise[i * a_dim + a];
+    }
+  }
+  __syncthreads();
+  for (int64_t t = 0; t < T; ++t) {
+    double nz_next[kDeepMaxA];
+    if (j == 0 && t + 1 < T)
+      for (int a = 0; a < a_dim; ++a) nz_next[a] = noise[((t + 1) * n + i) * a_dim + a];
+    // layer 1 (nf = 2)
+    if (c0)
+      shid[0][j] = fmax(
+          __dadd_rn(__dadd_rn(__dmul_rn(sx[0], w1a), __dmul_rn(sx[1], w1b)), bb1), 0.0);
+    __syncthreads();
+    // layers 2 .. L: layer l + 1 reads shid[(l - 1) & 1] and writes shid[l & 1]; the last one
+    // keeps its column in a register for the mean layer
+    double hv = 0.0;
+    {
+      int64_t woff = 0;
+      int boff = 0, soff = 0;
+      for (int l = 1; l < L; ++l) {
+        const int hp = sh.h[l - 1], hl = sh.h[l], kl = sh.kl[l];
+        hv = 0.0;
+        if (j < hl) {
+          const double bias = bt[boff + j];  // (an L2 hit, in flight under the column sum)
+          hv = fmax(deep_column<kDeepU>(sW + soff, Wt + woff + j, shid[(l - 1) & 1], hp, hl, kl,
+                                        j) + bias, 0.0);
+        }
+        if (l + 1 < L) {
+          if (j < hl) shid[l & 1][j] = hv;
+          __syncthreads();
+        }
+        woff += (int64_t)hp * hl;
+        boff += hl;
+        soff += kl * hl;
+      }
+    }
+    // mean layer: per-wave partial sums over its 64 columns, then waves in order
+#pragma unroll
+    for (int a = 0; a < kDeepMaxA; ++a) {
+      if (a < a_dim) {
+        double q = wm[a] * hv;
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m, kWave);
+        if (lane == 0) spart[wave][a] = q;
+      }
+    }
+    __syncthreads();
+    if (j == 0) {
+      double act[kDeepMaxA];
+      for (int a = 0; a < a_dim; ++a) {
+        double mu = spart[0][a];
+        for (int w = 1; w < nwL; ++w) mu += spart[w][a];
+        mu += bm[a];
+        // output = mean + randn * exp(log_std)   (policy.py:59)
+        act[a] = __dadd_rn(mu, __dmul_rn(nz[a], sd[a]));
+        actions_rec[(i * T + t) * a_dim + a] = (float)act[a];
+      }
+      if (t + 1 < T)
+        for (int a = 0; a < a_dim; ++a) nz[a] = nz_next[a];
+      if (ENV == 0) {
+        MountainCar::step(p, v, act[0]);
+        sx[0] = p;
+        sx[1] = v;
+      } else {
+        GridWorld::step(gx, gy, act[0], act[1]);
+        sx[0] = (double)gx;
+        sx[1] = (double)gy;
+      }
+      states_rec[(i * (T + 1) + t + 1) * 2 + 0] = (float)sx[0];
+      states_rec[(i * (T + 1) + t + 1) * 2 + 1] = (float)sx[1];
+      if (visited) {
+        visited[(i * T + t) * 2 + 0] = sx[0];
+        visited[(i * T + t) * 2 + 1] = sx[1];
+      }
+    }
+    __syncthreads();
+  }
+  if (j == 0 && final_state) {
+    final_state[2 * i] = sx[0];
+    final_state[2 * i + 1] = sx[1];
+  }
+}
+
+constexpr size_t kDeepWorkspaceBytes = 256;  // the error-word header
+
+// Host-side validation shared by the two entry points; the error text names the limits.
+static bool deep_shape_ok(int env_id, int n_hidden, const int* widths, int a_dim) {
+  bool ok = env_id >= 0 && env_id <= 1 && n_hidden >= kDeepMinL && n_hidden <= kDeepMaxL &&
+            widths && a_dim >= 1 && a_dim <= kDeepMaxA && !(env_id == 1 && a_dim != 2);
+  for (int l = 0; ok && l < n_hidden; ++l) ok = widths[l] >= 1 && widths[l] <= kDeepMaxH;
+  return ok;
+}
+
+static int deep_bad_args(const char* who) {
+  set_error("%s: bad arguments (env 0 or 1, %d <= n_hidden <= %d, 1 <= width <= %d, "
+            "1 <= a_dim <= %d, GridWorld a_dim = 2, no null pointers)",
+            who, kDeepMinL, kDeepMaxL, kDeepMaxH, kDeepMaxA);
+  return kErrBadArg;
+}
+
+}  // namespace envs
+}  // namespace mepol
+
+using namespace mepol;
+using namespace mepol::envs;
+
+extern "C" int mepol_rollout_deep_workspace_size(int64_t n, int64_t T, int n_hidden,
+                                                 const int* widths, int a_dim, size_t* bytes) {
+  // (the env does not change the size: MountainCar's a_dim range covers GridWorld's)
+  if (n < 0 || T < 0 || !bytes || !deep_shape_ok(0, n_hidden, widths, a_dim))
+    return deep_bad_args("mepol_rollout_deep_workspace_size");
+  *bytes = kDeepWorkspaceBytes;
+  return 0;
+}
+
+extern "C" int mepol_rollout_deep(int env_id, int n_hidden, const int* widths, const double* W1,
+                                  const double* b1, const double* Wt, const double* bt,
+                                  const double* Wm, const double* bm, const double* log_std,
+                                  int a_dim, const double* init64, const float* init32,
+                                  const double* noise, int64_t n, int64_t T, float* states_rec,
+                                  float* actions_rec, double* visited, double* final_state,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (n <= 0 || T <= 0) return 0;
+  if (!deep_shape_ok(env_id, n_hidden, widths, a_dim) || (env_id == 0 && !init64) ||
+      (env_id == 1 && !init32) || !W1 || !b1 || !Wt || !bt || !Wm || !bm || !log_std || !noise ||
+      !states_rec || !actions_rec)
+    return deep_bad_args("mepol_rollout_deep");
+  if (workspace && workspace_bytes < kDeepWorkspaceBytes) {
+    set_error("mepol_rollout_deep: workspace of %zu bytes, %zu needed", workspace_bytes,
+              kDeepWorkspaceBytes);
+    return kErrWorkspace;
+  }
+  DeepShape sh;
+  sh.L = n_hidden;
+  int wmax = 0;
+  for (int l = 0; l < kDeepMaxL; ++l) {
+    sh.h[l] = l < n_hidden ? widths[l] : 0;
+    sh.kl[l] = 0;
+    wmax = std::max(wmax, sh.h[l]);
+  }
+  // leading rows of the packed W_2^T .. W_L^T kept in LDS: whole rows, layer after layer, while
+  // they fit (MEPOL_ROLLOUT_KL caps their number); everything behind them streams
+  const char* klv = getenv("MEPOL_ROLLOUT_KL");
+  int rows_left = klv ? std::max(0, atoi(klv)) : INT_MAX;
+  int words_left = kDeepLdsBytes / (int)sizeof(double);
+  size_t lds = 0;
+  for (int l = 1; l < n_hidden; ++l) {
+    const int rows = std::min({sh.h[l - 1], words_left / sh.h[l], rows_left});
+    sh.kl[l] = rows;
+    words_left -= rows * sh.h[l];
+    rows_left -= rows;
+    lds += (size_t)rows * sh.h[l] * sizeof(double);
+    if (rows < sh.h[l - 1]) break;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (workspace) MEPOL_HIP(hipMemsetAsync(workspace, 0, kDeepWorkspaceBytes, st));
+  const dim3 g((unsigned)n), b((unsigned)((wmax + 63) / 64 * 64));
+#define MEPOL_DEEP(E)                                                                            \
+  do {                                                                                           \
+    MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<E>>(kDeepLdsBytes)));                         \
+    hipLaunchKernelGGL((rollout_deep_kernel<E>), g, b, lds, st, W1, b1, Wt, bt, Wm, bm, log_std, \
+                       a_dim, init64, init32, noise, n, T, states_rec, actions_rec, visited,     \
+                       final_state, sh);                                                         \
+  } while (0)
+  if (env_id == 0)
+    MEPOL_DEEP(0);
+  else
+    MEPOL_DEEP(1);
+#undef MEPOL_DEEP
+  MEPOL_CHECK_LAUNCH();
+  return 0;
+}

@@ -619,6 +619,44 @@ def rollout_mlp(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, states_rec
         call("mepol_rollout_mlp", *args, None, 0, _stream())
 
 
+def rollout_deep(env_id, layers, Wm, bm, log_std, init, noise, states_rec, actions_rec,
+                 visited=None):
+    """rollout_mlp for a ReLU policy with 3 to 6 hidden layers, layers = [(W1, b1), ..., (W_L,
+    b_L)] (widths <= 512, odd ones included): all T steps in one launch, one workgroup per
+    trajectory (csrc/rollout_deep.hip).  W_2 .. W_L are transposed and packed here per call."""
+    _require_device(init, noise, states_rec, actions_rec, visited, Wm, bm, log_std,
+                    *[t for p in layers for t in p])
+    T, n, a_dim = noise.shape
+    (W1, b1), rest = layers[0], layers[1:]
+    fan_in = [2] + [W.shape[0] for W, _ in layers]
+    if (any(tuple(W.shape) != (b.numel(), f) for (W, b), f in zip(layers, fan_in))
+            or tuple(Wm.shape) != (a_dim, fan_in[-1]) or bm.numel() != a_dim
+            or log_std.numel() != a_dim or tuple(init.shape) != (n, 2)
+            or tuple(states_rec.shape) != (n, T + 1, 2) or tuple(actions_rec.shape) != (n, T, a_dim)
+            or (visited is not None and tuple(visited.shape) != (n, T, 2))):
+        raise ValueError("rollout_deep: tensor shapes do not fit the policy / batch")
+    f64 = [t for p in layers for t in p] + [Wm, bm, log_std, noise] + (
+        [visited] if visited is not None else []) + ([init] if env_id == 0 else [])
+    if (any(t.dtype != torch.float64 for t in f64) or (env_id == 1 and init.dtype != torch.float32)
+            or states_rec.dtype != torch.float32 or actions_rec.dtype != torch.float32
+            or not (states_rec.is_contiguous() and actions_rec.is_contiguous()
+                    and (visited is None or visited.is_contiguous()))):
+        raise ValueError("rollout_deep: f64 policy / noise / visited, f32 contiguous records")
+    widths = (ctypes.c_int * len(layers))(*[W.shape[0] for W, _ in layers])
+    Wt = torch.cat([W.t().reshape(-1) for W, _ in rest])
+    bt = torch.cat([b.reshape(-1) for _, b in rest])
+    # (contiguous copies stay referenced until the launch is queued)
+    W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
+                                                                     noise))
+    init64 = init if env_id == 0 else None
+    init32 = init if env_id == 1 else None
+    ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
+                       a_dim)
+    call("mepol_rollout_deep", env_id, len(layers), widths, ptr(W1), ptr(b1), ptr(Wt), ptr(bt),
+         ptr(Wm), ptr(bm), ptr(log_std), a_dim, ptr(init64), ptr(init32), ptr(noise), n, T,
+         ptr(states_rec), ptr(actions_rec), ptr(visited), None, ptr(ws), ws.numel(), _stream())
+
+
 def rollout_mlp_plan(n, h0, h1, a_dim):
     """{"workgroups_per_traj", "k_chunks"}: the form mepol_rollout_mlp takes for this shape and
     the layer-2 summation order it commits to (oracle.rollout_kordered's k_chunks)."""

@@ -262,6 +262,25 @@ int mepol_policy_forward_masked(const double* x, int64_t n, int in_features, con
                                 double* h1_out, double* z2_out, double* mu_out, double* logp_out,
                                 uint16_t* h1_mask_out, void* stream);
 
+/* The same forward with the row tile of its split form (even hidden0: layer 1, then the z2 GEMM
+ * and head) chosen by the caller: row_tile 0 = automatic (what the two calls above do), 64, 32
+ * or 16 = that many rows per workgroup of the z2 / head kernel; any other value is
+ * MEPOL_ERR_BAD_ARG.  h1_mask_out may be null.  Every output is the same bits for every tile.
+ * The one-kernel form (odd hidden0) has 64-row blocks only: 32 or 16 is MEPOL_ERR_UNSUPPORTED. */
+int mepol_policy_forward_tiled(const double* x, int64_t n, int in_features, const double* W1,
+                               const double* b1, int hidden0, const double* W2, const double* b2,
+                               int hidden1, const double* Wm, const double* bm,
+                               const double* log_std, const double* actions, int action_dim,
+                               double* h1_out, double* z2_out, double* mu_out, double* logp_out,
+                               uint16_t* h1_mask_out, int row_tile, void* stream);
+
+/* Host only (no GPU call): *row_tile = the rows per workgroup automatic selection takes for n
+ * rows: the shortest of 16 and 32 whose grid ceil(n / tile) fits the 256 CUs (16 to n = 4096,
+ * 32 to n = 8192), 64 from there on (so for every n >= 16384) and for an odd hidden0.  n > 0,
+ * in_features <= 64, hidden1 <= 320. */
+int mepol_policy_forward_plan_info(int64_t n, int in_features, int hidden0, int hidden1,
+                                   int* row_tile);
+
 /* Backward of the first layer fused into the dh1 GEMM: dW1 [h0, in] and db1 [h0] (nullable) of
  * h1 = relu(x W1^T + b1) from dz2 [n, k] and W2t = W2^T [h0, k] (dh1 = dz2 W2 stays on chip,
  * masked by h1 > 0 from the forward's h1 [n, h0]).  k even, in_features <= 63, dz2 and W2t

@@ -75,6 +75,10 @@ SIGNATURES = {
     "mepol_policy_forward_masked": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
                                     _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
                                     _c_vp, _c_vp, _c_vp, _c_vp],
+    "mepol_policy_forward_tiled": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
+                                   _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
+                                   _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
+    "mepol_policy_forward_plan_info": [_c_i64, _c_int, _c_int, _c_int, ctypes.POINTER(_c_int)],
     "mepol_hidden_backward_workspace_size": [_c_i64, _c_int, ctypes.POINTER(_c_sz)],
     "mepol_hidden_backward": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
                               _c_sz, _c_vp],

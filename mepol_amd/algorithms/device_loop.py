@@ -60,17 +60,18 @@ def _opt_kind(optimizer):
     return None
 
 
-def supported(batch, behavioral_policy, target_policy, optimizer):
+def supported(batch, behavioral_policy, target_policy, optimizer, min_rows=None):
     """True when the iteration can run as a graph: the reference's 2-layer ReLU GaussianPolicy
     (f64, fused-head sizes), a dense particle grid, Adam/RMSprop with MEPOL's settings over
-    exactly the target's parameters."""
+    exactly the target's parameters.  min_rows: the caller's own batch floor instead of
+    policy.fused_min_rows() (the sharded iteration keeps 16384 rows per rank)."""
     if os.environ.get("MEPOL_DEVICE_LOOP", "1") == "0":
         return False
     if not isinstance(target_policy, GaussianPolicy) or target_policy is behavioral_policy:
         return False
     if not (batch.dense and batch.states_flat.is_cuda):
         return False
-    if not target_policy._fused_head_ok(batch.states_flat, batch.actions_flat):
+    if not target_policy._fused_head_ok(batch.states_flat, batch.actions_flat, min_rows):
         return False
     layers = [m for m in target_policy.net if isinstance(m, nn.Linear)]
     if len(layers) != 2 or target_policy.num_features > 64:
@@ -664,8 +665,10 @@ class MultiLayerIteration(DeviceIteration):
         Wm, bm, ls = self.named[2 * L:]
         ops.layer_forward(self.x, Ws[0], bs[0], out=self.hs[0])
         for l in range(1, L - 1):
-            ops.gemm_nt(self.hs[l - 1], Ws[l], bias=bs[l], relu=True, out=self.hs[l])
-        ops.gemm_nt(self.hs[L - 2], Ws[L - 1], out=self.zL)
+            ops.gemm_nt(self.hs[l - 1], Ws[l], bias=bs[l], relu=True, out=self.hs[l],
+                        variant=ops.gemm_nt_variant(self.N, Ws[l].shape[0]))
+        ops.gemm_nt(self.hs[L - 2], Ws[L - 1], out=self.zL,
+                    variant=ops.gemm_nt_variant(self.N, Ws[L - 1].shape[0]))
         ops.head_forward(self.zL, Wm, bm, ls, self.act, bz=bs[L - 1], mu_out=self.mu,
                          logp_out=self.logp)
 

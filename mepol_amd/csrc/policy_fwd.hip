@@ -308,18 +308,46 @@ __global__ __launch_bounds__(256) void layer1_kernel(const double* __restrict__ 
 // no barrier in the K loop; LDS only for the head epilogue's sum of the 4 column waves.
 // tools/z2_probe.py: the bare GEMM at 50.7 TF/s (C3) against 45 in the
 // fused kernel's k-tile loop.
+//
+// Row tile: FO fragments of 16 rows per wave, 64 (FO = 4, the large-batch kernel), 32 or 16 rows
+// per workgroup.  A batch under 16384 rows gives fewer 64-row workgroups than the chip has CUs;
+// launch_split then takes a shorter tile (zh::pick_tile).  An output element does not depend on
+// FO: acc[t][u] is its own chain over the same k order, and the epilogue sums a row over u,
+// over the 16 lanes (reduce_scatter_g) and over the 4 waves in wave order, whatever t is.
 namespace zh {
-constexpr int FO = 4, FI = 5, NW = 4, NS = 2, NL = FO + FI;
-constexpr int BM = 16 * FO;  // rows per workgroup (x 320 columns)
+constexpr int FI = 5, NW = 4, NS = 2;
+constexpr int kCUs = 256;  // gfx950: the grid a short tile has to fit in to be picked
+// Waves per SIMD asked of the compiler: 2 for every FO.  FO = 4 needs it (160 accumulator
+// registers in the 256-VGPR budget).  FO = 2 and FO = 1 have 80 and 40, but asking for 4 waves
+// (128 VGPRs) spilled both (620 and 12 B of scratch per lane: the epilogue holds the
+// accumulators next to 40 doubles of Wm; the spilled FO = 2 ran 196 us where this one takes
+// 52), and pick_tile gives them at most one workgroup per CU, one wave per SIMD, so a higher
+// occupancy would not be used.  At 2 they compile to 178 and 136 VGPRs, no scratch.
+constexpr int kOcc = 2;
+// Automatic tile: the shortest of {16, 32} whose grid ceil(n / tile) still fits one workgroup
+// per CU, else 64: 16 rows to n = 4096, 32 to n = 8192, 64 from there on, so every n >= 16384
+// launches the 64-row kernel.  The cut points are measured ("Batches under 16,384
+// rows"): a tile's time is flat while its grid is within the 256 CUs and steps up by about half
+// with the first workgroup that has to share a CU (16 rows: 46 -> 68 us between 4000 and 6000
+// rows at 2 -> [300, 300] -> 1; 32 rows: 61 -> 85 us between 8160 and 10000), which puts it
+// behind the next taller tile.  The rule first planned, the tallest tile whose grid reaches the
+// CU count, would run 16 rows up to 8160 and 32 up to 16320: slower than this one from 4097 on.
+inline int pick_tile(int64_t n) {
+  for (int tile = 16; tile < 64; tile *= 2)
+    if ((n + tile - 1) / tile <= kCUs) return tile;
+  return 64;
+}
 }  // namespace zh
 
-__global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(2))) void z2_head_kernel(
+template <int FO>
+__global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(zh::kOcc))) void z2_head_kernel(
     const double* __restrict__ h1, int64_t N, int H1, const double* __restrict__ W2,
     const double* __restrict__ b2, int H2, const double* __restrict__ Wm,
     const double* __restrict__ bm, const double* __restrict__ log_std,
     const double* __restrict__ act, int A, double* __restrict__ z2_out,
     double* __restrict__ mu_out, double* __restrict__ logp_out) {
-  constexpr int FO = zh::FO, FI = zh::FI, NW = zh::NW, NS = zh::NS, NL = zh::NL, ZM = zh::BM;
+  constexpr int FI = zh::FI, NW = zh::NW, NS = zh::NS, NL = FO + FI;
+  constexpr int ZM = 16 * FO;  // rows per workgroup (x 320 columns)
   __shared__ double sMu[NW * ZM * 4];
   const int tid = threadIdx.x, l = tid & 63, fr = l & 15, g = l >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -390,7 +418,8 @@ __global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(2))
   // 4 actions per pass (the fused kernel's 8 would hold 40 more registers next to the 160 of
   // the accumulators)
   constexpr int AC = 4;
-  const int er = tid >> 2, ea = tid & 3;  // combine step: row er of the block, action slot ea
+  // combine step: row er of the block, action slot ea (threads 4 ZM and up have no row)
+  const int er = tid >> 2, ea = tid & 3;
   double lp = 0.0;
   for (int a0 = 0; a0 < A; a0 += AC) {
     double wmv[FI][AC];
@@ -423,7 +452,7 @@ __global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(2))
       const int a = a0 + ea;
       const int64_t r = row0 + er;
       double term = 0.0;
-      if (a < A && r < N) {
+      if (er < ZM && a < A && r < N) {
         double m = sMu[(0 * ZM + er) * AC + ea];
 #pragma unroll
         for (int v = 1; v < NW; ++v) m += sMu[(v * ZM + er) * AC + ea];
@@ -440,7 +469,7 @@ __global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(2))
     }
     __syncthreads();
   }
-  if (ea == 0 && row0 + er < N) logp_out[row0 + er] = lp;
+  if (ea == 0 && er < ZM && row0 + er < N) logp_out[row0 + er] = lp;
 }
 
 #ifndef MEPOL_L1_RG
@@ -452,14 +481,23 @@ template <int FP>
 int launch_split(const double* x, int64_t n, int F, const double* W1, const double* b1, int H1,
                  const double* W2, const double* b2, int H2, const double* Wm, const double* bm,
                  const double* log_std, const double* act, int A, double* h1, double* z2,
-                 double* mu, double* logp, uint16_t* mask, hipStream_t st) {
-  const unsigned blocks = (unsigned)((n + 63) / 64);
+                 double* mu, double* logp, uint16_t* mask, int row_tile, hipStream_t st) {
+  const int tile = row_tile ? row_tile : zh::pick_tile(n);
+  const unsigned blocks = (unsigned)((n + tile - 1) / tile);
   constexpr int RG = kLayer1RowGroups;
   hipLaunchKernelGGL((layer1_kernel<FP, RG>), dim3((unsigned)((n + 64 * RG - 1) / (64 * RG))),
                      dim3(256), 0, st, x, n, F, W1, b1, H1, h1, mask);
   MEPOL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(z2_head_kernel, dim3(blocks), dim3(64 * zh::NW), 0, st, h1, n, H1, W2, b2,
-                     H2, Wm, bm, log_std, act, A, z2, mu, logp);
+#define MEPOL_Z2(FOV)                                                                       \
+  hipLaunchKernelGGL(z2_head_kernel<FOV>, dim3(blocks), dim3(64 * zh::NW), 0, st, h1, n, H1, W2, \
+                     b2, H2, Wm, bm, log_std, act, A, z2, mu, logp)
+  if (tile == 64)
+    MEPOL_Z2(4);
+  else if (tile == 32)
+    MEPOL_Z2(2);
+  else
+    MEPOL_Z2(1);
+#undef MEPOL_Z2
   MEPOL_CHECK_LAUNCH();
   return 0;
 }
@@ -481,32 +519,41 @@ int launch(const double* x, int64_t n, int F, const double* W1, const double* b1
 }  // namespace pfwd
 }  // namespace mepol
 
-static int policy_forward(const double* x, int64_t n, int in_features, const double* W1,
-                          const double* b1, int hidden0, const double* W2, const double* b2,
-                          int hidden1, const double* Wm, const double* bm,
+// row_tile: 0 = automatic (zh::pick_tile), 64 / 32 / 16 = that tile of the split form.
+static int policy_forward(const char* who, const double* x, int64_t n, int in_features,
+                          const double* W1, const double* b1, int hidden0, const double* W2,
+                          const double* b2, int hidden1, const double* Wm, const double* bm,
                           const double* log_std, const double* actions, int action_dim,
                           double* h1_out, double* z2_out, double* mu_out, double* logp_out,
-                          uint16_t* h1_mask_out, void* stream) {
+                          uint16_t* h1_mask_out, int row_tile, void* stream) {
   using namespace mepol::pfwd;
   if (n < 0 || in_features <= 0 || in_features > 64 || hidden0 <= 0 || hidden1 <= 0 ||
       hidden1 > BN || action_dim <= 0 || !x || !W1 || !b1 || !W2 || !b2 || !Wm || !bm ||
       !log_std || !actions || !h1_out || !z2_out || !mu_out || !logp_out ||
       ((uintptr_t)W2 & 15)) {
-    mepol::set_error("mepol_policy_forward: bad arguments (in_features <= 64, hidden1 <= %d)",
-                     BN);
+    mepol::set_error("%s: bad arguments (in_features <= 64, hidden1 <= %d)", who, BN);
     return mepol::kErrBadArg;
   }
-  if (n == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
+  if (row_tile != 0 && row_tile != 64 && row_tile != 32 && row_tile != 16) {
+    mepol::set_error("%s: row_tile %d (0 = automatic, 64, 32 or 16)", who, row_tile);
+    return mepol::kErrBadArg;
+  }
   // the split form (layer1_kernel + z2_head_kernel) needs 16-B aligned h1 rows; C3 forward
   // 1.19 ms against the one-kernel form's 1.32 (profiles/r5/f64/forward_split_ab.txt)
   const bool split = hidden0 % 2 == 0 && ((uintptr_t)h1_out & 15) == 0;
+  if (!split && row_tile != 0 && row_tile != 64) {
+    mepol::set_error("%s: the one-kernel form (odd hidden0) has 64-row blocks only, not %d", who,
+                     row_tile);
+    return mepol::kErrUnsupported;
+  }
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
 #define MEPOL_PF(FPV)                                                                        \
   {                                                                                          \
   if (split)                                                                                 \
     return launch_split<FPV>(x, n, in_features, W1, b1, hidden0, W2, b2, hidden1, Wm, bm,     \
                              log_std, actions, action_dim, h1_out, z2_out, mu_out, logp_out, \
-                             h1_mask_out, st);                                               \
+                             h1_mask_out, row_tile, st);                                     \
   return (hidden0 % 2 == 0 && hidden0 >= 2)                                                  \
              ? launch<FPV, true>(x, n, in_features, W1, b1, hidden0, W2, b2, hidden1, Wm, bm, \
                                  log_std, actions, action_dim, h1_out, z2_out, mu_out,        \
@@ -531,8 +578,9 @@ extern "C" int mepol_policy_forward(const double* x, int64_t n, int in_features,
                                     const double* actions, int action_dim, double* h1_out,
                                     double* z2_out, double* mu_out, double* logp_out,
                                     void* stream) {
-  return policy_forward(x, n, in_features, W1, b1, hidden0, W2, b2, hidden1, Wm, bm, log_std,
-                        actions, action_dim, h1_out, z2_out, mu_out, logp_out, nullptr, stream);
+  return policy_forward("mepol_policy_forward", x, n, in_features, W1, b1, hidden0, W2, b2,
+                        hidden1, Wm, bm, log_std, actions, action_dim, h1_out, z2_out, mu_out,
+                        logp_out, nullptr, 0, stream);
 }
 
 extern "C" int mepol_policy_forward_masked(const double* x, int64_t n, int in_features,
@@ -547,7 +595,36 @@ extern "C" int mepol_policy_forward_masked(const double* x, int64_t n, int in_fe
     mepol::set_error("mepol_policy_forward_masked: h1_mask_out is null");
     return mepol::kErrBadArg;
   }
-  return policy_forward(x, n, in_features, W1, b1, hidden0, W2, b2, hidden1, Wm, bm, log_std,
-                        actions, action_dim, h1_out, z2_out, mu_out, logp_out, h1_mask_out,
-                        stream);
+  return policy_forward("mepol_policy_forward_masked", x, n, in_features, W1, b1, hidden0, W2,
+                        b2, hidden1, Wm, bm, log_std, actions, action_dim, h1_out, z2_out,
+                        mu_out, logp_out, h1_mask_out, 0, stream);
 }
+
+extern "C" int mepol_policy_forward_tiled(const double* x, int64_t n, int in_features,
+                                          const double* W1, const double* b1, int hidden0,
+                                          const double* W2, const double* b2, int hidden1,
+                                          const double* Wm, const double* bm,
+                                          const double* log_std, const double* actions,
+                                          int action_dim, double* h1_out, double* z2_out,
+                                          double* mu_out, double* logp_out,
+                                          uint16_t* h1_mask_out, int row_tile, void* stream) {
+  return policy_forward("mepol_policy_forward_tiled", x, n, in_features, W1, b1, hidden0, W2, b2,
+                        hidden1, Wm, bm, log_std, actions, action_dim, h1_out, z2_out, mu_out,
+                        logp_out, h1_mask_out, row_tile, stream);
+}
+
+// Host only (no GPU call): the rows per workgroup automatic selection gives the z2 / head part.
+// The one-kernel form (odd hidden0) always has 64.
+extern "C" int mepol_policy_forward_plan_info(int64_t n, int in_features, int hidden0,
+                                              int hidden1, int* row_tile) {
+  using namespace mepol::pfwd;
+  if (n <= 0 || in_features <= 0 || in_features > 64 || hidden0 <= 0 || hidden1 <= 0 ||
+      hidden1 > BN || !row_tile) {
+    mepol::set_error("mepol_policy_forward_plan_info: bad arguments (in_features <= 64, "
+                     "hidden1 <= %d)", BN);
+    return mepol::kErrBadArg;
+  }
+  *row_tile = hidden0 % 2 == 0 ? zh::pick_tile(n) : BM;
+  return 0;
+}
+

@@ -396,12 +396,22 @@ def h1_mask_buffer(n, hidden0, device):
     return torch.empty((n, (hidden0 + 15) // 16), dtype=torch.int16, device=device)
 
 
+def policy_forward_plan(n, in_features, hidden0, hidden1):
+    """{"row_tile"}: the rows per workgroup policy_forward(row_tile=0) takes for its z2 / head
+    kernel at n rows (host only: mepol_policy_forward_plan_info)."""
+    tile = ctypes.c_int()
+    call("mepol_policy_forward_plan_info", n, in_features, hidden0, hidden1, ctypes.byref(tile))
+    return {"row_tile": tile.value}
+
+
 def policy_forward(x, W1, b1, W2, b2, Wm, bm, log_std, act, h1_out=None, z2_out=None,
-                   mu_out=None, logp_out=None, mask_out=None):
+                   mu_out=None, logp_out=None, mask_out=None, row_tile=0):
     """One-kernel forward of the two-hidden-layer Gaussian policy: returns (h1, z2, mu, logp)
     with h1 = relu(x W1^T + b1), z2 = h1 W2^T (pre-bias), mu = relu(z2 + b2) Wm^T + bm and
     logp = sum_a log N(act | mu, exp(log_std) + 1e-7).  With mask_out (h1_mask_buffer) the
-    kernel also writes relu'(h1) as bits for dh1_layer1_backward(mask=...)."""
+    kernel also writes relu'(h1) as bits for dh1_layer1_backward(mask=...).  row_tile: rows per
+    workgroup of the z2 / head kernel, 0 = chosen from n (policy_forward_plan), or 64 / 32 / 16
+    (the same bits for each; anything else raises MepolInputError)."""
     n, f = x.shape
     h0, h1w, a = W1.shape[0], W2.shape[0], Wm.shape[0]
     dev = x.device
@@ -413,16 +423,12 @@ def policy_forward(x, W1, b1, W2, b2, Wm, bm, log_std, act, h1_out=None, z2_out=
     z2 = buf(z2_out, (n, h1w))
     mu = buf(mu_out, (n, a))
     logp = buf(logp_out, (n,))
-    if mask_out is None:
-        call("mepol_policy_forward", ptr(x), n, f, ptr(W1), ptr(b1), h0, ptr(W2), ptr(b2), h1w,
-             ptr(Wm), ptr(bm), ptr(log_std), ptr(act), a, ptr(h1), ptr(z2), ptr(mu), ptr(logp),
-             _stream())
-    else:
+    if mask_out is not None:
         assert mask_out.shape == (n, (h0 + 15) // 16) and mask_out.dtype == torch.int16
         assert mask_out.is_contiguous()
-        call("mepol_policy_forward_masked", ptr(x), n, f, ptr(W1), ptr(b1), h0, ptr(W2), ptr(b2),
-             h1w, ptr(Wm), ptr(bm), ptr(log_std), ptr(act), a, ptr(h1), ptr(z2), ptr(mu),
-             ptr(logp), ptr(mask_out), _stream())
+    call("mepol_policy_forward_tiled", ptr(x), n, f, ptr(W1), ptr(b1), h0, ptr(W2), ptr(b2), h1w,
+         ptr(Wm), ptr(bm), ptr(log_std), ptr(act), a, ptr(h1), ptr(z2), ptr(mu), ptr(logp),
+         ptr(mask_out), int(row_tile), _stream())
     return h1, z2, mu, logp
 
 
@@ -512,6 +518,20 @@ def hidden_backward(dz_out, W, h_in, ws=None, dz_out_buf=None, db_out=None):
     call("mepol_hidden_backward", ptr(dz_out), n, o, ptr(W), ptr(h_in), i, ptr(dz), ptr(db),
          ptr(ws), ws.numel(), _stream())
     return dz, db
+
+
+GEMM_NT_CUS = 256          # gfx950
+GEMM_NT_KEEP_ROWS = 16384  # from here on variant 0 always (the large-batch path, as measured)
+
+
+def gemm_nt_variant(n, m):
+    """The gemm_nt tiling of the deep policy's layers for an [n, m] output: variant 0 (128 x 160
+    tiles) when its grid reaches the CU count, and for every n >= 16384; variant 2 (64 x 160,
+    twice the workgroups) for a smaller batch whose variant-0 grid would leave CUs idle."""
+    if n >= GEMM_NT_KEEP_ROWS:
+        return 0
+    tiles = -(-n // 128) * -(-m // 160)
+    return 0 if tiles >= GEMM_NT_CUS else 2
 
 
 def gemm_nt(A, B, bias=None, relu=False, out=None, variant=0):

@@ -28,6 +28,7 @@ import torch
 
 from . import ops as _hip_ops
 from .algorithms.device_loop import DeviceIteration, capture_guard
+from .policy import SPLITK_MIN_ROWS
 
 
 def prepare_nccl_env():
@@ -280,7 +281,10 @@ class ShardedEpoch:
         from .algorithms import device_loop as DL
 
         view = _LocalView(self)
-        if not DL.supported(view, beh, tgt, optimizer) or _GRAPH_STATE.get("disabled"):
+        # the per-rank floor stays at 16384 rows whatever policy.FUSED_MIN_ROWS is: no test
+        # covers a smaller shard under graph replay with collectives
+        if (not DL.supported(view, beh, tgt, optimizer, min_rows=SPLITK_MIN_ROWS)
+                or _GRAPH_STATE.get("disabled")):
             return None
         if self.dist.get_backend(self.group) != "nccl":  # only RCCL collectives can be captured
             return None

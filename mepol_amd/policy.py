@@ -8,13 +8,18 @@ Parameters are float64 (the reference's dtype, src/utils/dtypes.py:3) and are in
 the CPU generator in the reference's order (Linear defaults, then xavier_uniform on
 ``mean.weight`` and the ``net`` weights, policy.py:36-41), so a given torch seed yields the
 reference's initial weights; the module can then be moved to the GPU with ``.to(device)``.
-Large f64 batches of a ReLU policy take the library's HIP kernels end to end: two hidden
-layers through _TwoLayerLogp, three to six even-width hidden layers through _MultiLayerLogp
-(f64 matrix-core GEMMs, csrc/gemm.hip, csrc/wgrad.hip; fused head, csrc/head.hip).  Every other
-shape (one hidden layer, odd widths, other activations, small batches) runs its Linear layers
-on PyTorch-ROCm (hipBLASLt/rocBLAS GEMMs).
+f64 batches of a ReLU policy from FUSED_MIN_ROWS rows (MEPOL_FUSED_MIN_ROWS overrides it) take
+the library's HIP kernels end to end: two hidden layers through _TwoLayerLogp, three to six
+even-width hidden layers through _MultiLayerLogp (f64 matrix-core GEMMs, csrc/gemm.hip,
+csrc/wgrad.hip; fused head, csrc/head.hip).  Under 16384 rows the forward takes a shorter row
+tile (csrc/policy_fwd.hip, zh::pick_tile) and the deep policy's GEMMs the 64-row variant
+(ops.gemm_nt_variant), so that the grid still covers the chip; the reference's MountainCar
+script (8,000 particles) runs there.  Every other shape (one hidden layer, odd widths, other
+activations, batches under the floor) runs its Linear layers on PyTorch-ROCm (hipBLASLt/rocBLAS
+GEMMs), and so do mean_action and the rocBLAS paths here, whose floor stays SPLITK_MIN_ROWS.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -23,6 +28,16 @@ LOG_STD_EPS = 1e-7  # src/utils/dtypes.py:7, used inside get_log_p (policy.py:49
 LOG_2PI = math.log(2 * math.pi)
 SPLITK_MIN_ROWS = 16384
 SPLITK = 32
+# Rows from which get_log_p and the graph loop take the HIP kernels (_fused_head_ok only; the
+# rocBLAS paths above keep SPLITK_MIN_ROWS).  MEPOL_FUSED_MIN_ROWS overrides it, read per call.
+# The value is the smallest batch of tools/small_batch_bench.py's sweep from which the kernel
+# path beat the nn.Linear path for both policies ("Batches under 16,384 rows").
+FUSED_MIN_ROWS = 500
+
+
+def fused_min_rows():
+    v = os.environ.get("MEPOL_FUSED_MIN_ROWS")
+    return int(v) if v else FUSED_MIN_ROWS
 
 
 def _split_count(n):
@@ -166,10 +181,12 @@ class _MultiLayerLogp(torch.autograd.Function):
         L = (len(params) - 3) // 2
         Ws, bs = params[0:2 * L:2], params[1:2 * L:2]
         Wm, bm, log_std = params[2 * L:]
+        n = x.shape[0]
         hs = [ops.layer_forward(x, Ws[0], bs[0])]
         for l in range(1, L - 1):
-            hs.append(ops.gemm_nt(hs[-1], Ws[l], bias=bs[l], relu=True))
-        zL = ops.gemm_nt(hs[-1], Ws[L - 1])
+            hs.append(ops.gemm_nt(hs[-1], Ws[l], bias=bs[l], relu=True,
+                                  variant=ops.gemm_nt_variant(n, Ws[l].shape[0])))
+        zL = ops.gemm_nt(hs[-1], Ws[L - 1], variant=ops.gemm_nt_variant(n, Ws[L - 1].shape[0]))
         mu, logp = ops.head_forward(zL, Wm, bm, log_std, actions, bz=bs[L - 1])
         ctx.L = L
         ctx.save_for_backward(x, actions, zL, mu, Wm, log_std, bs[L - 1], *Ws[1:], *hs)
@@ -234,8 +251,10 @@ class GaussianPolicy(nn.Module):
             h = _apply_linear(layer, h) if isinstance(layer, nn.Linear) else layer(h)
         return _apply_linear(self.mean, h)
 
-    def _fused_head_ok(self, states, actions):
-        return (states.is_cuda and states.dim() == 2 and states.shape[0] >= SPLITK_MIN_ROWS
+    def _fused_head_ok(self, states, actions, min_rows=None):
+        """min_rows: the caller's own floor (the sharded iteration's), default fused_min_rows()."""
+        floor = fused_min_rows() if min_rows is None else min_rows
+        return (states.is_cuda and states.dim() == 2 and states.shape[0] >= floor
                 and self.activation is nn.ReLU and self.action_dim <= 32
                 and self.mean.in_features <= 512 and states.dtype == torch.float64
                 and actions.dtype == torch.float64)

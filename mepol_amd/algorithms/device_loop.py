@@ -22,9 +22,12 @@ before each replay.  After a rejected step the caller restores theta and calls `
 Results equal the eager path (autograd through the same kernels) up to the optimizer's
 rounding order; tests/test_gpu_device_loop.py checks both against each other and the oracle.
 
-A ReLU policy with three to six even-width hidden layers runs the same iteration with its own
-network part (MultiLayerIteration: per-layer static activations, gemm_nt forward, a
-hidden_backward chain beside the weight gradients; tests/test_gpu_multilayer_policy.py).
+DeviceIteration holds everything that does not depend on the network's depth (the static inputs,
+the replay machinery, the body above) and reaches the network through three methods:
+_alloc_network (the parameter order and the network's buffers), forward and _backward.  A ReLU
+policy with three to six even-width hidden layers runs the same iteration with its own three
+(MultiLayerIteration: per-layer static activations, gemm_nt forward, a hidden_backward chain
+beside the weight gradients; tests/test_gpu_multilayer_policy.py).
 """
 import contextlib
 import gc
@@ -60,11 +63,9 @@ def _opt_kind(optimizer):
     return None
 
 
-def supported(batch, behavioral_policy, target_policy, optimizer, min_rows=None):
-    """True when the iteration can run as a graph: the reference's 2-layer ReLU GaussianPolicy
-    (f64, fused-head sizes), a dense particle grid, Adam/RMSprop with MEPOL's settings over
-    exactly the target's parameters.  min_rows: the caller's own batch floor instead of
-    policy.fused_min_rows() (the sharded iteration keeps 16384 rows per rank)."""
+def _supported(batch, behavioral_policy, target_policy, optimizer, min_rows, shape_ok):
+    """The conditions every graph iteration shares; shape_ok(hidden widths, input features) is the
+    caller's condition on the network."""
     if os.environ.get("MEPOL_DEVICE_LOOP", "1") == "0":
         return False
     if not isinstance(target_policy, GaussianPolicy) or target_policy is behavioral_policy:
@@ -74,32 +75,7 @@ def supported(batch, behavioral_policy, target_policy, optimizer, min_rows=None)
     if not target_policy._fused_head_ok(batch.states_flat, batch.actions_flat, min_rows):
         return False
     layers = [m for m in target_policy.net if isinstance(m, nn.Linear)]
-    if len(layers) != 2 or target_policy.num_features > 64:
-        return False
-    params = list(target_policy.parameters())
-    if len(params) != 7 or any(p.dtype != torch.float64 or not p.is_contiguous() or
-                               p.device != batch.device for p in params):
-        return False
-    if _opt_kind(optimizer) is None:
-        return False
-    return [id(p) for p in optimizer.param_groups[0]["params"]] == [id(p) for p in params]
-
-
-def supported_multilayer(batch, behavioral_policy, target_policy, optimizer):
-    """supported()'s conditions for the ReLU policies with three to six even-width hidden
-    layers, which MultiLayerIteration runs (policy.multilayer_ok: the shapes _MultiLayerLogp
-    takes).  supported() itself stays False for them: the sharded iteration (parallel.py) asks
-    it and is written for the two-layer parameter list."""
-    if os.environ.get("MEPOL_DEVICE_LOOP", "1") == "0":
-        return False
-    if not isinstance(target_policy, GaussianPolicy) or target_policy is behavioral_policy:
-        return False
-    if not (batch.dense and batch.states_flat.is_cuda):
-        return False
-    if not target_policy._fused_head_ok(batch.states_flat, batch.actions_flat):
-        return False
-    layers = [m for m in target_policy.net if isinstance(m, nn.Linear)]
-    if not multilayer_ok([m.out_features for m in layers], target_policy.num_features):
+    if not shape_ok([m.out_features for m in layers], target_policy.num_features):
         return False
     params = list(target_policy.parameters())
     if len(params) != 2 * len(layers) + 3 or any(
@@ -109,6 +85,23 @@ def supported_multilayer(batch, behavioral_policy, target_policy, optimizer):
     if _opt_kind(optimizer) is None:
         return False
     return [id(p) for p in optimizer.param_groups[0]["params"]] == [id(p) for p in params]
+
+
+def supported(batch, behavioral_policy, target_policy, optimizer, min_rows=None):
+    """True when the iteration can run as a graph: the reference's 2-layer ReLU GaussianPolicy
+    (f64, fused-head sizes), a dense particle grid, Adam/RMSprop with MEPOL's settings over
+    exactly the target's parameters.  min_rows: the caller's own batch floor instead of
+    policy.fused_min_rows() (the sharded iteration keeps 16384 rows per rank)."""
+    return _supported(batch, behavioral_policy, target_policy, optimizer, min_rows,
+                      lambda widths, nf: len(widths) == 2 and nf <= 64)
+
+
+def supported_multilayer(batch, behavioral_policy, target_policy, optimizer):
+    """supported()'s conditions for the ReLU policies with three to six even-width hidden
+    layers, which MultiLayerIteration runs (policy.multilayer_ok: the shapes _MultiLayerLogp
+    takes).  supported() itself stays False for them: the sharded iteration (parallel.py) asks
+    it and is written for the two-layer parameter list."""
+    return _supported(batch, behavioral_policy, target_policy, optimizer, None, multilayer_ok)
 
 
 _guard_depth, _guard_restore = 0, False
@@ -148,7 +141,12 @@ def _scalar_dtype():
 
 
 class DeviceIteration:
-    """Static buffers + captured graph for one (policy, optimizer, batch shape, k, constants)."""
+    """Static buffers + captured graph for one (policy, optimizer, batch shape, k, constants).
+
+    The constructor, the body and the replay machinery are the same for every network depth.
+    The network is behind three methods, which a subclass for another depth replaces:
+    _alloc_network (self.named and the network's own buffers, workspaces and streams), forward
+    and _backward; here they are the two-hidden-layer ones."""
 
     def __init__(self, target_policy, optimizer, batch, k, G, B, ns, eps):
         # the cache below is keyed weakly by the target policy: a strong reference here would
@@ -156,14 +154,10 @@ class DeviceIteration:
         self._tgt_ref, self.opt = weakref.ref(target_policy), optimizer
         self.kind = _opt_kind(optimizer)
         self.params = list(target_policy.parameters())  # optimizer / state order
-        l1, l2 = [m for m in target_policy.net if isinstance(m, nn.Linear)]
-        self.named = (l1.weight, l1.bias, l2.weight, l2.bias, target_policy.mean.weight,
-                      target_policy.mean.bias, target_policy.log_std)
         self.k, self.G, self.B, self.ns, self.eps = k, float(G), float(B), float(ns), float(eps)
         dev = batch.device
         self.device = dev
         self.N, self.nt, self.T, self.kp1 = batch.N, batch.num_traj, batch.T, batch.kp1
-        W1, _, W2, _, Wm, _, _ = self.named
         f64 = dict(dtype=torch.float64, device=dev)
         self.x = torch.empty_like(batch.states_flat)
         self.act = torch.empty_like(batch.actions_flat)
@@ -173,24 +167,12 @@ class DeviceIteration:
         self.logp_b = torch.empty((self.nt, self.T), **f64)
         off, rows = batch.csr(k)
         self.csr_off, self.csr_rows = torch.empty_like(off), torch.empty_like(rows)
-        self.h1 = torch.empty((self.N, W1.shape[0]), **f64)
-        self.z2 = torch.empty((self.N, W2.shape[0]), **f64)
+        self.fork = torch.cuda.Stream(device=dev)  # the weight gradients' stream
+        self._alloc_network(target_policy, batch)
+        Wm = self.named[-3]  # [actions, last hidden width]
         self.mu = torch.empty((self.N, Wm.shape[0]), **f64)
         self.logp = torch.empty(self.N, **f64)
-        self.fused_fwd = (ops.policy_forward_ok(self.x.shape[1], W2.shape[0])
-                          and os.environ.get("MEPOL_FUSED_FWD", "1") != "0")
-        self.fused_dh1 = (ops.dh1_layer1_ok(self.x.shape[1], W2.shape[0])
-                          and os.environ.get("MEPOL_FUSED_DH1", "1") != "0")
         self.neg_one = torch.full((), -1.0, **f64)
-        # relu'(h1) as bits, written by the fused forward beside h1 and read by the fused dh1
-        # backward in place of h1 (1/64 of the bytes its epilogue waits for)
-        self.h1_mask = (ops.h1_mask_buffer(self.N, W1.shape[0], dev)
-                        if self.fused_fwd and self.fused_dh1 else None)
-        # W2^T only for the dh1 kernel without the mask or with an odd h0 (otherwise dh1 reads
-        # W2 as stored, mepol_dh1_layer1_backward_w2)
-        self.dh1_w2 = self.h1_mask is not None and W1.shape[0] % 2 == 0
-        self.W2t = (torch.empty((W2.shape[1], W2.shape[0]), **f64)
-                    if self.fused_dh1 and not self.dh1_w2 else None)
         # every body takes its optimizer step through _optim_step, which leaves theta_t in the
         # replay's shadow (off_policy_optimization then copies it into last_valid only when it
         # needs it, not after every accepted step)
@@ -212,16 +194,40 @@ class DeviceIteration:
         self.g_cur = torch.zeros(self.N, **f64)   # dH/dW at theta_t
         self.out_cur = torch.zeros(4, **f64)      # entropy_forward sums at theta_t
         # scratch owned by this graph (never the eager per-stream cache, whose buffers can be
-        # replaced while a captured graph still holds their addresses)
-        self.ws_head = ops.head_workspace(self.N, W2.shape[0], Wm.shape[0], dev)
+        # replaced while a captured graph still holds their addresses); _alloc_network's
+        # workspaces likewise, one per kernel call site
+        self.ws_head = ops.head_workspace(self.N, Wm.shape[1], Wm.shape[0], dev)
+        self._init_state()
+
+    def _alloc_network(self, target_policy, batch):
+        """self.named (the parameters in the order _backward returns their gradients) and what
+        forward / _backward need beyond the shared inputs: here the two-layer activations, the
+        fused kernels' switches and buffers, the workspaces and the dh1 stream."""
+        l1, l2 = [m for m in target_policy.net if isinstance(m, nn.Linear)]
+        self.named = (l1.weight, l1.bias, l2.weight, l2.bias, target_policy.mean.weight,
+                      target_policy.mean.bias, target_policy.log_std)
+        W1, _, W2, _, _, _, _ = self.named
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.h1 = torch.empty((self.N, W1.shape[0]), **f64)
+        self.z2 = torch.empty((self.N, W2.shape[0]), **f64)
+        self.fused_fwd = (ops.policy_forward_ok(self.x.shape[1], W2.shape[0])
+                          and os.environ.get("MEPOL_FUSED_FWD", "1") != "0")
+        self.fused_dh1 = (ops.dh1_layer1_ok(self.x.shape[1], W2.shape[0])
+                          and os.environ.get("MEPOL_FUSED_DH1", "1") != "0")
+        # relu'(h1) as bits, written by the fused forward beside h1 and read by the fused dh1
+        # backward in place of h1 (1/64 of the bytes its epilogue waits for)
+        self.h1_mask = (ops.h1_mask_buffer(self.N, W1.shape[0], dev)
+                        if self.fused_fwd and self.fused_dh1 else None)
+        # W2^T only for the dh1 kernel without the mask or with an odd h0 (otherwise dh1 reads
+        # W2 as stored, mepol_dh1_layer1_backward_w2)
+        self.dh1_w2 = self.h1_mask is not None and W1.shape[0] % 2 == 0
+        self.W2t = (torch.empty((W2.shape[1], W2.shape[0]), **f64)
+                    if self.fused_dh1 and not self.dh1_w2 else None)
         self.ws_layer = ops.layer_workspace(self.N, W1.shape[1], W1.shape[0], dev)
         self.ws_dh1 = ops.dh1_layer1_workspace(self.N, W1.shape[0], W1.shape[1], dev)
         self.ws_wgrad = ops.weight_grad_workspace(self.N, W2.shape[0], W2.shape[1], dev)
-        self.graph = None
-        self.fork = torch.cuda.Stream(device=dev)
         self.s_gemm = torch.cuda.Stream(device=dev)
-        self._batch_id = None
-        self._init_state()
 
     @property
     def tgt(self):
@@ -334,7 +340,6 @@ class DeviceIteration:
             pairs.append((self.logp_b, logp_b))
         for dst, src in pairs:
             dst.copy_(src)
-        self._batch_id = id(batch)
 
     @torch.no_grad()
     def forward(self):
@@ -412,7 +417,6 @@ class DeviceIteration:
 
     @torch.no_grad()
     def _body(self):
-        W1, b1, W2, b2, Wm, bm, ls = self.named
         nt, T, N, k = self.nt, self.T, self.N, self.k
         lt = self.logp.view(nt, T)
         self._scal_in()
@@ -422,10 +426,9 @@ class DeviceIteration:
         gamma, partials, nparts = ops.entropy_gamma(g, w, self.csr_off, self.csr_rows)
         grad = ops.entropy_reverse_scan(gamma, w, partials, nparts, self.offsets, nt, T,
                                         self.neg_one)
-        # through the policy (the _TwoLayerLogp backward)
-        dW1, db1, dW2, db2, dWm, dbm, dls = self._backward(grad.view(-1))
-        # optimizer.step() (mepol.py:280)
-        grad_of = {id(p): g for p, g in zip(self.named, (dW1, db1, dW2, db2, dWm, dbm, dls))}
+        # through the policy (the _TwoLayerLogp / _MultiLayerLogp backward): gradients in
+        # self.named's order, taken to the optimizer's for optimizer.step() (mepol.py:280)
+        grad_of = {id(p): g for p, g in zip(self.named, self._backward(grad.view(-1)))}
         self._optim_step([grad_of[id(p)] for p in self.params])
         # compute_kl at theta_t+1 (mepol.py:435, :157-174).  The pass with the entropy
         # constants also yields the KL sum (its terms do not depend on them) and the next
@@ -452,13 +455,6 @@ class DeviceIteration:
     # control outputs go to, pinned host buffers through memcpy nodes of the graph itself.
     def _scal_in(self):
         ops.memcpy_async(self.scal, self.scal_host)
-
-    def _emit(self, a, ia, b, ib, cur, nw, n):
-        """vals_host <- (a[ia], b[ib]) through a memcpy node; cur[:n] <- nw[:n]."""
-        if not (a is self.vals and b is self.vals and (ia, ib) == (0, 1)):
-            torch.stack((a[ia], b[ib]), out=self.vals)
-        cur[:n].copy_(nw[:n])
-        ops.memcpy_async(self.vals_host, self.vals)
 
     @torch.no_grad()
     def _prime(self):
@@ -573,7 +569,6 @@ class DeviceIteration:
             torch._foreach_add_([self.opt.state[p]["step"] for p in self.params], -1.0)
             self._next = par
 
-
     def release(self):
         """Wait for replays in flight and free the captured graphs (before the process group
         whose collectives a sharded graph captured is destroyed)."""
@@ -596,67 +591,28 @@ class MultiLayerIteration(DeviceIteration):
 
     dW_l = dz_l^T h_{l-1} needs only dz_l, so every weight gradient runs on the forked stream
     beside the chain that produces dz_{l-1}, as dW2 runs beside dh1 in the two-layer iteration;
-    the head's parameter-gradient reduces follow the first of them there.  The two-layer
-    iteration's code is left as it is (the sharded iteration builds on it), so the constructor
-    and the body are restated here for the longer parameter list."""
+    the head's parameter-gradient reduces follow the first of them there.  The constructor and
+    the body are DeviceIteration's; only _alloc_network, forward and _backward are replaced."""
 
-    def __init__(self, target_policy, optimizer, batch, k, G, B, ns, eps):
-        self._tgt_ref, self.opt = weakref.ref(target_policy), optimizer
-        self.kind = _opt_kind(optimizer)
-        self.params = list(target_policy.parameters())  # optimizer / state order
+    def _alloc_network(self, target_policy, batch):
         layers = [m for m in target_policy.net if isinstance(m, nn.Linear)]
         L = self.L = len(layers)
         # (W_1, b_1, ..., W_L, b_L, Wm, bm, log_std): the order _backward returns gradients in
         self.named = tuple(t for m in layers for t in (m.weight, m.bias)) + (
             target_policy.mean.weight, target_policy.mean.bias, target_policy.log_std)
-        self.k, self.G, self.B, self.ns, self.eps = k, float(G), float(B), float(ns), float(eps)
-        dev = batch.device
-        self.device = dev
-        N = self.N = batch.N
-        self.nt, self.T, self.kp1 = batch.num_traj, batch.T, batch.kp1
+        N, dev = self.N, self.device
         f64 = dict(dtype=torch.float64, device=dev)
-        self.x = torch.empty_like(batch.states_flat)
-        self.act = torch.empty_like(batch.actions_flat)
-        self.D = torch.empty_like(batch.D)
-        self.idx32T = torch.empty_like(batch.idx32T)
-        self.offsets = torch.empty_like(batch.offsets)
-        self.logp_b = torch.empty((self.nt, self.T), **f64)
-        off, rows = batch.csr(k)
-        self.csr_off, self.csr_rows = torch.empty_like(off), torch.empty_like(rows)
         widths = [m.out_features for m in layers]
-        nf, a = self.x.shape[1], target_policy.mean.out_features
         self.hs = [torch.empty((N, w), **f64) for w in widths[:-1]]   # h_1 .. h_{L-1}
         self.zL = torch.empty((N, widths[-1]), **f64)
         # dz_{L-1}, dz_{L-2}, ... alternate between two buffers (dz_L is the head's)
         self.dz_buf = [torch.empty(N * max(widths[:-1]), **f64) for _ in range(min(2, L - 1))]
-        self.mu = torch.empty((N, a), **f64)
-        self.logp = torch.empty(N, **f64)
         self.fused_fwd = self.fused_dh1 = False  # the two-layer iteration's fused kernels
-        self.neg_one = torch.full((), -1.0, **f64)
-        self.tracks_shadow = True
-        self.speculative = os.environ.get("MEPOL_SPECULATE", "1") != "0"
-        self._bufs = [self._make_bufs(dev) for _ in range(2 if self.speculative else 1)]
-        self._use(0)
-        self._inflight = []
-        self._next = 0
-        self._last = 0
-        self._events = [torch.cuda.Event() for _ in self._bufs]
-        self.graphs = [None] * len(self._bufs)
-        self.w_cur = torch.zeros(N, **f64)
-        self.g_cur = torch.zeros(N, **f64)
-        self.out_cur = torch.zeros(4, **f64)
-        # one scratch buffer per kernel call site, owned by this graph (never the eager
-        # per-stream cache, whose buffers can be replaced while a graph holds their addresses)
-        self.ws_head = ops.head_workspace(N, widths[-1], a, dev)
-        self.ws_layer = ops.layer_workspace(N, nf, widths[0], dev)
+        self.ws_layer = ops.layer_workspace(N, self.x.shape[1], widths[0], dev)
         self.ws_wgrad = [None] + [ops.weight_grad_workspace(N, widths[l], widths[l - 1], dev)
                                   for l in range(1, L)]
         self.ws_hidden = [None] + [ops.hidden_backward_workspace(N, widths[l - 1], dev)
                                    for l in range(1, L)]
-        self.graph = None
-        self.fork = torch.cuda.Stream(device=dev)
-        self._batch_id = None
-        self._init_state()
 
     @torch.no_grad()
     def forward(self):
@@ -710,24 +666,6 @@ class MultiLayerIteration(DeviceIteration):
         cur.wait_stream(self.fork)
         del dzL, dz  # kept until the forked stream has joined: it read them
         return tuple(t for pair in zip(dW, db) for t in pair) + (dWm, dbm, dls)
-
-    @torch.no_grad()
-    def _body(self):
-        """DeviceIteration._body with the gradients mapped through the longer self.named."""
-        nt, T, N, k = self.nt, self.T, self.N, self.k
-        lt = self.logp.view(nt, T)
-        self._scal_in()
-        w, g = self.w_cur, self.g_cur
-        gamma, partials, nparts = ops.entropy_gamma(g, w, self.csr_off, self.csr_rows)
-        grad = ops.entropy_reverse_scan(gamma, w, partials, nparts, self.offsets, nt, T,
-                                        self.neg_one)
-        grad_of = {id(p): g for p, g in zip(self.named, self._backward(grad.view(-1)))}
-        self._optim_step([grad_of[id(p)] for p in self.params])
-        self.forward()
-        ops.iw_forward(lt, self.logp_b, self.offsets, N, w_out=self.w_cur)
-        ops.entropy_forward(self.w_cur, self.idx32T, self.D, k, self.ns, self.G, self.B,
-                            self.eps, g_out=self.g_cur, out4=self.out_cur, vals=self.vals)
-        ops.memcpy_async(self.vals_host, self.vals)
 
 
 _CACHE = weakref.WeakKeyDictionary()  # target policy -> DeviceIteration

@@ -13,6 +13,8 @@ import pytest
 import scipy.special
 import torch
 
+from loop_runs import _assert_same_run, _run
+
 pytestmark = pytest.mark.gpu
 
 TILES = (64, 32, 16)
@@ -134,74 +136,7 @@ def test_logp_and_gradients_below_the_old_floor(cuda, monkeypatch, n, nf, hidden
 # ---- 3. graph loop == eager == oracle --------------------------------------------------------
 MC = dict(NT=20, T=400, NF=2, A=1, K=4, HID=[300, 300])   # scripts/tae/mountain_car.sh's batch
 DEEP = dict(NT=10, T=200, NF=2, A=2, K=4, HID=[64, 48, 32])
-MAX_BT = 4
-
-
-def _setup(opt_name, lr, c, seed=5):
-    from mepol_amd.algorithms import mepol as M
-    from mepol_amd.policy import GaussianPolicy
-
-    NT, T, NF, A, K, HID = c["NT"], c["T"], c["NF"], c["A"], c["K"], c["HID"]
-    rng = np.random.default_rng(seed)
-    states = rng.standard_normal((NT, T + 1, NF)).astype(np.float32)
-    actions = (0.5 * rng.standard_normal((NT, T, A))).astype(np.float32)
-    dev = torch.device("cuda")
-    st = torch.as_tensor(states, dtype=torch.float64, device=dev)
-    ac = torch.as_tensor(actions, dtype=torch.float64, device=dev)
-    rtl = torch.full((NT, 1), T, dtype=torch.int64, device=dev)
-    nxt = torch.as_tensor(states[:, 1:].reshape(-1, NF), device=dev)
-    torch.manual_seed(seed)
-    beh = GaussianPolicy(HID, NF, A).to(dev)
-    tgt = GaussianPolicy(HID, NF, A).to(dev)
-    last = GaussianPolicy(HID, NF, A).to(dev)
-    tgt.load_state_dict(beh.state_dict())
-    last.load_state_dict(beh.state_dict())
-    opt_cls = torch.optim.Adam if opt_name == "adam" else torch.optim.RMSprop
-    opt = opt_cls(tgt.parameters(), lr=lr)
-    batch = M.make_particle_batch(st, ac, rtl, nxt, K)
-    return M, (states, actions), beh, tgt, last, opt, batch
-
-
-def _run(monkeypatch, graph, opt_name, lr, kl_threshold, c, max_off_iters=6):
-    """tests/test_gpu_device_loop.py::_run at the shapes above."""
-    from mepol_amd.algorithms import device_loop
-
-    NT, NF, K = c["NT"], c["NF"], c["K"]
-    monkeypatch.setenv("MEPOL_DEVICE_LOOP", "1" if graph else "0")
-    M, raw, beh, tgt, last, opt, (st, ac, rl, _, D, I) = _setup(opt_name, lr, c)
-    G = float(scipy.special.gamma(NF / 2 + 1))
-    B = float(np.log(K) - scipy.special.digamma(K))
-    trace = []
-    res = M.off_policy_optimization(
-        opt, beh, tgt, last, st, ac, NT, rl, D, I, K, G, B, NF, 0.0, kl_threshold, max_off_iters,
-        True, 2, MAX_BT, lr,
-        on_accept=lambda n, e, kl, l: trace.append((n, float(e), float(kl), l)))
-    it = device_loop._CACHE.get(tgt)
-    params = torch.cat([p.detach().reshape(-1) for p in last.parameters()]).cpu().numpy()
-    state = opt.state_dict()["state"]
-    steps = [float(state[i]["step"]) for i in sorted(state)]
-    moments = np.concatenate([state[i][key].detach().reshape(-1).cpu().numpy()
-                              for i in sorted(state) for key in sorted(state[i])
-                              if key != "step"])
-    tparams = torch.cat([p.detach().reshape(-1) for p in tgt.parameters()]).cpu().numpy()
-    return dict(H=float(res[0]), n=res[1], bt=res[2], lr=res[3], trace=trace, params=params,
-                steps=steps, used=it is not None, raw=raw, D=D, I=I, moments=moments,
-                tparams=tparams, it_type=type(it).__name__ if it is not None else None)
-
-
-def _assert_same_run(g, e):
-    """tests/test_gpu_device_loop.py::_assert_same_run."""
-    assert g["used"] and not e["used"]
-    assert (g["n"], g["bt"], g["lr"]) == (e["n"], e["bt"], e["lr"])
-    assert g["steps"] == e["steps"]
-    assert len(g["trace"]) == len(e["trace"])
-    for a, b in zip(g["trace"], e["trace"]):
-        assert a[0] == b[0] and a[3] == b[3]
-        np.testing.assert_allclose(a[1:3], b[1:3], rtol=1e-9, atol=1e-12)
-    np.testing.assert_allclose(g["H"], e["H"], rtol=1e-9)
-    np.testing.assert_allclose(g["params"], e["params"], rtol=1e-8, atol=1e-11)
-    np.testing.assert_allclose(g["tparams"], e["tparams"], rtol=1e-8, atol=1e-11)
-    np.testing.assert_allclose(g["moments"], e["moments"], rtol=1e-8, atol=1e-14)
+MAX_BT = 4  # the backtracking tries loop_runs._run passes to the loop
 
 
 def _oracle_loop(g, c, opt_name, lr, kl_threshold, max_off_iters):
@@ -279,11 +214,11 @@ def test_small_batch_graph_loop(cuda, monkeypatch, shape, opt_name, case):
         lr, thr = (1e-5 if opt_name == "adam" else 1e-6), 10.0
     else:
         lr, thr = 5e-2, 1e-3
-    g = _run(monkeypatch, True, opt_name, lr, thr, c)
-    e = _run(monkeypatch, False, opt_name, lr, thr, c)
+    g = _run(monkeypatch, True, opt_name, lr, thr, cfg=c)
+    e = _run(monkeypatch, False, opt_name, lr, thr, cfg=c)
     print("graph", g["n"], g["bt"], g["lr"], g["trace"])
     # the graph run is the iteration object of device_loop._CACHE
-    assert g["it_type"] == ("DeviceIteration" if shape == "mountaincar" else
+    assert g["it_type"].__name__ == ("DeviceIteration" if shape == "mountaincar" else
                             "MultiLayerIteration")
     if case == "accepted":
         assert g["n"] == 6 and g["bt"] == 1
@@ -297,10 +232,10 @@ def test_small_batch_graph_loop_backtracked_step_accepted(cuda, monkeypatch):
     """Adam at 1e-3 on the MountainCar-script shape: the first tries exceed KL 10, a halved
     learning rate passes, and the loop ends on that accepted backtracked step."""
     monkeypatch.delenv("MEPOL_FUSED_MIN_ROWS", raising=False)
-    g = _run(monkeypatch, True, "adam", 1e-3, 10.0, MC)
-    e = _run(monkeypatch, False, "adam", 1e-3, 10.0, MC)
+    g = _run(monkeypatch, True, "adam", 1e-3, 10.0, cfg=MC)
+    e = _run(monkeypatch, False, "adam", 1e-3, 10.0, cfg=MC)
     print("graph", g["n"], g["bt"], g["lr"], g["trace"])
-    assert g["it_type"] == "DeviceIteration" and g["bt"] > 1 and g["n"] == 1
+    assert g["it_type"].__name__ == "DeviceIteration" and g["bt"] > 1 and g["n"] == 1
     _assert_same_run(g, e)
     _assert_matches_oracle(g, _oracle_loop(g, MC, "adam", 1e-3, 10.0, 6))
 

@@ -338,6 +338,47 @@ int mepol_hidden_backward(const double* dz_out, int64_t n, int out_features, con
                           const double* h_in, int in_features, double* dz_in, double* db_in,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Fisher-vector product of TRPO's policy step (src/algorithms/trpo.py:369-406) ------------
+ * Replaces hessian_vector_product's double backward through policy(states): at theta = theta_0
+ * the Hessian of KL(theta_0 || theta) over the network parameters is (1/n) sum_i J_i^T
+ * diag(1 / (exp(2 log_std) + 1e-7)) J_i with J_i = d mu_i / d theta, so one product is a tangent
+ * (forward-mode) pass, the entry points below, and the backward pass of the kernels above
+ * (mepol_weight_grad, mepol_hidden_backward, mepol_layer_backward) over activations kept from
+ * one forward.  relu'(0) = 0 as torch.  Every entry point only enqueues; n <= 0 returns 0
+ * without a launch; every other argument is validated on the host before any launch.
+ *
+ * Input layer: t_out [n, out] = (x dW^T + db) * (h > 0) for x [n, in] (in <= 64), the tangent
+ * direction dW [out, in], db [out] and the forward's h = relu(x W^T + b) [n, out]. */
+int mepol_layer_tangent(const double* x, int64_t n, int in_features, const double* dW,
+                        const double* db, int out_features, const double* h, double* t_out,
+                        void* stream);
+/* Hidden layer h_out = relu(h_in W^T + b) on the f64 matrix cores: t_out [n, m] = (t_in W^T +
+ * h_in dW^T + db) * (mask_src + mask_bias > 0) for the incoming tangent t_in [n, k], h_in [n, k],
+ * W and the direction dW [m, k] as stored, db [m]; the ReLU mask is taken from mask_src [n, m]
+ * plus mask_bias [m] (nullable: pass h_out with a null bias, or the pre-bias z with b).  Both
+ * products accumulate in the same MFMA accumulators.  k even; t_in, h_in, W and dW 16-byte
+ * aligned; `variant` = mepol_gemm_nt's tilings (0 = default, 2 = the 64-row one). */
+int mepol_hidden_tangent(const double* t_in, const double* h_in, int64_t n, int k, const double* W,
+                         const double* dW, const double* db, int m, const double* mask_src,
+                         const double* mask_bias, double* t_out, int variant, void* stream);
+/* Mean layer: c_out [n, a_dim] = scale[a] * (sum_j t[r][j] Wm[a][j] + relu(z[r][j] + bz[j])
+ * dWm[a][j] + dbm[a]) for the last hidden layer's tangent t and pre-bias pre-activation z
+ * [n, hidden], its bias bz (nullable), Wm and the direction dWm [a_dim, hidden], dbm [a_dim];
+ * scale [a_dim] is a DEVICE vector (the caller's 1 / ((exp(2 log_std) + 1e-7) n)).
+ * hidden <= 512, a_dim <= 32 (beyond: MEPOL_ERR_UNSUPPORTED). */
+int mepol_mean_tangent(const double* t, const double* z, int64_t n, int hidden, const double* bz,
+                       const double* Wm, const double* dWm, const double* dbm, const double* scale,
+                       int a_dim, double* c_out, void* stream);
+/* Mean-layer backward from a cotangent c [n, a_dim] on mu (mepol_head_backward with d mu given
+ * and no dlog_std): dWm [a_dim, hidden] = c^T relu(z + bz), dbm [a_dim] = column sums of c,
+ * dz [n, hidden] (nullable) = (c Wm) * (z + bz > 0), dbz [hidden] (nullable) = column sums of dz.
+ * Row sums go through fixed-order partials (the same bits on every call); workspace from
+ * mepol_mean_backward_workspace_size.  hidden <= 512, a_dim <= 32. */
+int mepol_mean_backward_workspace_size(int64_t n, int hidden, int a_dim, size_t* bytes);
+int mepol_mean_backward(const double* c, const double* z, int64_t n, int hidden, const double* bz,
+                        const double* Wm, int a_dim, double* dz, double* dWm, double* dbm,
+                        double* dbz, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- environments -------------------------------------------------------------------------
  * Replace MountainCarContinuous.step (src/envs/mountain_car_wall.py:13-45) and
  * GridWorldContinuous.step (src/envs/gridworld_continuous.py:128-154), batched. */

@@ -84,6 +84,14 @@ SIGNATURES = {
                               _c_sz, _c_vp],
     "mepol_gemm_nt": [_c_vp, _c_i64, _c_int, _c_i64, _c_vp, _c_int, _c_i64, _c_vp, _c_int, _c_vp,
                       _c_i64, _c_int, _c_vp],
+    "mepol_layer_tangent": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp],
+    "mepol_hidden_tangent": [_c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_vp,
+                             _c_vp, _c_vp, _c_int, _c_vp],
+    "mepol_mean_tangent": [_c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int,
+                           _c_vp, _c_vp],
+    "mepol_mean_backward_workspace_size": [_c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)],
+    "mepol_mean_backward": [_c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
+                            _c_vp, _c_vp, _c_vp, _c_sz, _c_vp],
     "mepol_step_mountaincar": [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp],
     "mepol_step_gridworld": [_c_vp, _c_vp, _c_i64, _c_vp],
     "mepol_rollout_step": [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_i64,

@@ -58,7 +58,9 @@ struct Cfg {
 // B[k][m, m + 1] (consecutive lanes consecutive m: coalesced) and writes the pair into LDS rows
 // m and m + 1 of the [BN][KT] image (two 8-B stores).  Lets dh1 = dz2 W2 read the Linear weight
 // as stored instead of a per-step W2^T copy.
-template <int WR, int WC, int FR, int FC, bool DEEP = false, bool BT = false>
+// ZERO = false: acc is added to, not zeroed first (a second operand pair summed into the same
+// accumulators: hidden_tangent_kernel).
+template <int WR, int WC, int FR, int FC, bool DEEP = false, bool BT = false, bool ZERO = true>
 __device__ __forceinline__ void gemm_mainloop(const double* __restrict__ A, int64_t N, int K,
                                               int64_t lda, const double* __restrict__ B, int M,
                                               int64_t ldb, int64_t row0, int col0, double* lds,
@@ -128,10 +130,12 @@ __device__ __forceinline__ void gemm_mainloop(const double* __restrict__ A, int6
     }
   };
 
+  if constexpr (ZERO) {
 #pragma unroll
-  for (int i = 0; i < FR; ++i)
+    for (int i = 0; i < FR; ++i)
 #pragma unroll
-    for (int j = 0; j < FC; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+      for (int j = 0; j < FC; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+  }
 
   const int fr = lane & 15, g = lane >> 4;
   // a lane's two slots in its fragment rows (every fragment row is fr mod 16: same swizzle)
@@ -473,6 +477,75 @@ __global__ __launch_bounds__(hbw::P::kThreads) void hidden_bwd_kernel(
   }
 }
 
+// ---- tangent (forward-mode) pass through a hidden layer (TRPO's Fisher-vector product) --------
+// t_out = (t_in W^T + h_in dW^T + db) . [mask_src + mask_bias > 0] for h_out = relu(h_in W^T + b):
+// the directional derivative of h_out along (dW, db) given the tangent t_in of h_in.  Two operand
+// pairs, (t_in, W) and (h_in, dW), both [.][K] row-major, run through gemm_mainloop one after the
+// other into the same accumulators (the second with ZERO = false; the first loop's last barrier
+// retired its LDS reads).  The epilogue loads the mask source at the accumulator positions in one
+// batch of unconditional loads (clamped addresses) before the first use, as hidden_bwd_kernel.
+// relu'(0) = 0 as torch: a pre-activation of exactly 0 gives t_out = 0.
+template <int WR, int WC, int FR, int FC>
+__global__ __launch_bounds__(WR * WC * 64) void hidden_tangent_kernel(
+    const double* __restrict__ t_in, const double* __restrict__ h_in, int64_t N, int K,
+    const double* __restrict__ W, const double* __restrict__ dW, const double* __restrict__ db,
+    int M, const double* __restrict__ mask_src, const double* __restrict__ mask_bias,
+    double* __restrict__ t_out) {
+  using P = Cfg<WR, WC, FR, FC>;
+  constexpr int BM = P::BM, BN = P::BN;
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wr = wave / WC, wc = wave % WC;
+  const int fr = frag_col(lane);
+  const int ncb = (M + BN - 1) / BN;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
+  const int64_t row0 = (int64_t)(tile / ncb) * BM;
+  const int col0 = (tile % ncb) * BN;
+  d4 acc[FR][FC];
+  gemm_mainloop<WR, WC, FR, FC>(t_in, N, K, K, W, M, K, row0, col0, lds, acc);
+  gemm_mainloop<WR, WC, FR, FC, false, false, false>(h_in, N, K, K, dW, M, K, row0, col0, lds,
+                                                     acc);
+
+  double mv[FC][FR][4];
+#pragma unroll
+  for (int i = 0; i < FR; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t r = row0 + wr * FR * 16 + i * 16 + frag_row(lane, q);
+      const double* mr = mask_src + min<int64_t>(r, N - 1) * M;
+#pragma unroll
+      for (int j = 0; j < FC; ++j) mv[j][i][q] = mr[min(col0 + wc * FC * 16 + j * 16 + fr, M - 1)];
+    }
+#pragma unroll
+  for (int j = 0; j < FC; ++j) {
+    const int c = col0 + wc * FC * 16 + j * 16 + fr;
+    if (c >= M) continue;
+    const double dbc = db[c];
+    const double mb = mask_bias ? mask_bias[c] : 0.0;
+#pragma unroll
+    for (int i = 0; i < FR; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t r = row0 + wr * FR * 16 + i * 16 + frag_row(lane, q);
+        if (r < N) t_out[r * M + c] = (mv[j][i][q] + mb > 0.0) ? acc[i][j][q] + dbc : 0.0;
+      }
+  }
+}
+
+template <int WR, int WC, int FR, int FC>
+int launch_tangent(const double* t_in, const double* h_in, int64_t n, int k, const double* W,
+                   const double* dW, const double* db, int m, const double* mask_src,
+                   const double* mask_bias, double* t_out, hipStream_t st) {
+  using P = Cfg<WR, WC, FR, FC>;
+  MEPOL_HIP((max_dynamic_lds<hidden_tangent_kernel<WR, WC, FR, FC>>((int)P::kLds)));
+  const int64_t tiles = (int64_t)((m + P::BN - 1) / P::BN) * ((n + P::BM - 1) / P::BM);
+  hipLaunchKernelGGL((hidden_tangent_kernel<WR, WC, FR, FC>), dim3((unsigned)tiles),
+                     dim3(P::kThreads), P::kLds, st, t_in, h_in, n, k, W, dW, db, m, mask_src,
+                     mask_bias, t_out);
+  MEPOL_CHECK_LAUNCH();
+  return 0;
+}
+
 template <int WR, int WC, int FR, int FC>
 int launch_nt(const double* A, int64_t n, int k, int64_t lda, const double* B, int m,
               int64_t ldb, const double* bias, int relu, double* C, int64_t ldc,
@@ -645,4 +718,45 @@ extern "C" int mepol_hidden_backward(const double* dz_out, int64_t n, int out_fe
   MEPOL_CHECK_LAUNCH();
   if (!db_in) return 0;
   return mepol::sum_records<kGroups>(part, nrb, (int64_t)m, ScatterDb{db_in}, st);
+}
+
+
+// Tangent pass through a hidden layer h_out = relu(h_in W^T + b): t_out [n, m] = (t_in W^T +
+// h_in dW^T + db) . [mask_src + mask_bias > 0] for t_in, h_in [n, k], W, dW [m, k] as stored,
+// db [m], mask_src [n, m], mask_bias [m] (nullable).  `variant` as for mepol_gemm_nt.
+extern "C" int mepol_hidden_tangent(const double* t_in, const double* h_in, int64_t n, int k,
+                                    const double* W, const double* dW, const double* db, int m,
+                                    const double* mask_src, const double* mask_bias,
+                                    double* t_out, int variant, void* stream) {
+  if (k <= 0 || m <= 0 || (k & 1) || !t_in || !h_in || !W || !dW || !db || !mask_src || !t_out ||
+      ((uintptr_t)t_in & 15) || ((uintptr_t)h_in & 15) || ((uintptr_t)W & 15) ||
+      ((uintptr_t)dW & 15)) {
+    mepol::set_error("mepol_hidden_tangent: bad arguments (k even and positive, m positive; "
+                     "t_in, h_in, W, dW, db, mask_src and t_out non-null; t_in, h_in, W and dW "
+                     "16-B aligned)");
+    return mepol::kErrBadArg;
+  }
+  const bool known = (variant >= 0 && variant <= 3) || (variant >= 5 && variant <= 10);
+  if (!known) {
+    mepol::set_error("mepol_hidden_tangent: unknown variant %d", variant);
+    return mepol::kErrBadArg;
+  }
+  if (n <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+#define MEPOL_TANGENT(WR, WC, FR, FC)                                                           \
+  return launch_tangent<WR, WC, FR, FC>(t_in, h_in, n, k, W, dW, db, m, mask_src, mask_bias,    \
+                                        t_out, st)
+  switch (variant) {  // mepol_gemm_nt's tilings
+    case 0: MEPOL_TANGENT(2, 2, 4, 5);
+    case 1: MEPOL_TANGENT(4, 2, 2, 5);
+    case 2: MEPOL_TANGENT(2, 2, 2, 5);
+    case 3: MEPOL_TANGENT(4, 1, 2, 10);
+    case 5: MEPOL_TANGENT(2, 2, 4, 4);
+    case 6: MEPOL_TANGENT(2, 4, 2, 5);
+    case 7: MEPOL_TANGENT(4, 1, 2, 5);
+    case 8: MEPOL_TANGENT(2, 5, 2, 5);
+    case 9: MEPOL_TANGENT(8, 1, 2, 5);
+    default: MEPOL_TANGENT(4, 2, 2, 4);
+  }
+#undef MEPOL_TANGENT
 }

@@ -456,6 +456,189 @@ static size_t ws_bytes(int64_t n, int hidden, int a_dim) {
   return sum_records_bytes<kRedGroups>(grid_bwd(std::max<int64_t>(n, 1)), m);
 }
 
+// ---- mean layer of TRPO's Fisher-vector product (algorithms/trpo.py) -------------------------
+// Tangent: c[r][a] = scale[a] (sum_j t[r][j] Wm[a][j] + relu(z[r][j] + bz[j]) dWm[a][j] + dbm[a]),
+// the directional derivative of mu along (tangent t of the last hidden layer, dWm, dbm), scaled.
+// head_fwd16_kernel's mapping: 16 lanes per row, 4 rows per wave, lane (r = l >> 4, q = l & 15)
+// owns columns q + 16 j; blockIdx.y picks a chunk of AP actions, whose Wm and dWm columns sit in
+// LDS as [j][a][q].  The column loop is a runtime loop (ncl = ceil(H / 16) steps).
+template <int AP>
+__global__ __launch_bounds__(256) void mean_tangent_kernel(
+    const double* __restrict__ t, const double* __restrict__ z, int64_t N, int H, int ncl,
+    const double* __restrict__ bz, const double* __restrict__ Wm, const double* __restrict__ dWm,
+    const double* __restrict__ dbm, const double* __restrict__ scale, int A,
+    double* __restrict__ c_out) {
+  extern __shared__ double smt[];  // Wm [ncl][AP][16] | dWm [ncl][AP][16] | bz [ncl 16]
+  double* sW = smt;
+  double* sD = sW + ncl * AP * 16;
+  double* sB = sD + ncl * AP * 16;
+  const int a0 = blockIdx.y * AP;
+  const int l = threadIdx.x & 63;
+  const int q = l & 15, r = l >> 4;
+  for (int e = threadIdx.x; e < ncl * AP * 16; e += blockDim.x) {
+    const int qq = e & 15, a = (e >> 4) % AP, j = (e >> 4) / AP;
+    const int c = qq + 16 * j;
+    const bool ok = c < H && a0 + a < A;
+    sW[e] = ok ? Wm[(int64_t)(a0 + a) * H + c] : 0.0;
+    sD[e] = ok ? dWm[(int64_t)(a0 + a) * H + c] : 0.0;
+  }
+  for (int e = threadIdx.x; e < ncl * 16; e += blockDim.x) sB[e] = (bz && e < H) ? bz[e] : 0.0;
+  __syncthreads();
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int64_t ngroups = (N + 3) / 4;
+  // lanes of a row with equal component: (16 / AP) of them; the lowest one writes
+  const bool writer = (q & ((16 / AP) - 1)) == 0;
+  for (int64_t gi = wave; gi < ngroups; gi += nwaves) {  // uniform per wave
+    const int64_t row = gi * 4 + r;
+    const int64_t rc = row < N ? row : N - 1;  // clamped row: loads in bounds, nothing written
+    const double* tr = t + rc * H;
+    const double* zr = z + rc * H;
+    double acc[AP];
+#pragma unroll
+    for (int a = 0; a < AP; ++a) acc[a] = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < ncl; ++j) {
+      const int c = q + 16 * j;
+      const int cc = c < H ? c : H - 1;
+      const double tl = tr[cc], zl = zr[cc];
+      const double tv = c < H ? tl : 0.0;
+      const double x = c < H ? fmax(zl + sB[c], 0.0) : 0.0;
+#pragma unroll
+      for (int a = 0; a < AP; ++a) {
+        acc[a] = fma(tv, sW[(j * AP + a) * 16 + q], acc[a]);
+        acc[a] = fma(x, sD[(j * AP + a) * 16 + q], acc[a]);
+      }
+    }
+    int ac;
+    const double v = reduce_scatter_g<AP, 16>(acc, l, ac);
+    const int a = a0 + ac;
+    if (row < N && a < A && writer) c_out[row * A + a] = scale[a] * (v + dbm[a]);
+  }
+}
+
+// Backward from a cotangent c [N][A] on mu: dWm = c^T relu(z + bz), dbm = sum_r c, dz = (c Wm) .
+// [z + bz > 0], dbz = sum_r dz.  head_bwd_wide_kernel's mapping for every action count: a block
+// of ceil(H / 64) waves owns one column per lane, walks rows grid-stride two at a time; c of a
+// row is lane-distributed (lane a holds component a) and broadcast through the wave's LDS slot.
+// One record [dW (A*H) | db (A) | dbz (H)] per block, summed by sum_records in a fixed order.
+template <int AP>
+__global__ __launch_bounds__(512) void mean_bwd_kernel(
+    const double* __restrict__ cm, const double* __restrict__ z, int64_t N, int H, int Hs,
+    const double* __restrict__ bz, const double* __restrict__ Wm, int A, double* __restrict__ dz,
+    double* __restrict__ part) {
+  static_assert(AP % 2 == 0 && AP <= 32, "pairs of components; one component per lane < 64");
+  constexpr int kRows = 2;
+  extern __shared__ double sWd[];  // [a < AP][c < Hs], then c[wave][row][a < AP]
+  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+  double2* sDm = reinterpret_cast<double2*>(sWd + AP * Hs) + w * (kRows * AP / 2);
+  for (int e = tid; e < AP * Hs; e += blockDim.x) {
+    const int a = e / Hs, c = e % Hs;
+    sWd[e] = (a < A && c < H) ? Wm[(int64_t)a * H + c] : 0.0;
+  }
+  __syncthreads();
+  const int c = tid;
+  const int cc = c < H ? c : H - 1;  // clamped column: loads in bounds, results discarded
+  const double bzc = (bz && c < H) ? bz[c] : 0.0;
+  double accW[AP];
+#pragma unroll
+  for (int a = 0; a < AP; ++a) accW[a] = 0.0;
+  double accz = 0.0, accb = 0.0;
+  const int64_t last = N - 1;
+  const int la = l < A ? l : A - 1;
+  struct Slot {
+    double z[kRows], cv[kRows];
+  };
+  auto load_slot = [&](Slot& s, int64_t i) {
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      const int64_t ic = i + r < N ? i + r : last;
+      s.z[r] = z[ic * H + cc];
+      s.cv[r] = cm[ic * A + la];
+    }
+  };
+  const int64_t stride = (int64_t)gridDim.x * kRows;
+  const int64_t i0 = (int64_t)__builtin_amdgcn_readfirstlane((int)blockIdx.x) * kRows;
+  Slot cur;
+  load_slot(cur, i0);
+  for (int64_t i = i0; i < N; i += stride) {
+    Slot s = cur;
+    load_slot(cur, i + stride);
+    double dm[kRows], x[kRows], zb[kRows], dh[kRows];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      const bool rowv = i + r < N;
+      dm[r] = (l < A && rowv) ? s.cv[r] : 0.0;  // 0 for lanes >= A and rows past N
+      accb += dm[r];
+      zb[r] = s.z[r] + bzc;
+      x[r] = rowv ? fmax(zb[r], 0.0) : 0.0;
+      dh[r] = 0.0;
+    }
+    // broadcast c through this wave's LDS slot (one wave's LDS ops complete in order)
+    if (l < AP) {
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) reinterpret_cast<double*>(sDm)[r * AP + l] = dm[r];
+    }
+    int cl = c;
+    asm volatile("" : "+v"(cl));  // keep the Wm LDS reads in the loop
+#pragma unroll
+    for (int a2 = 0; a2 < AP / 2; ++a2) {
+      const double w0 = sWd[(2 * a2) * Hs + cl];
+      const double w1 = sWd[(2 * a2 + 1) * Hs + cl];
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) {
+        const double2 sa = sDm[r * (AP / 2) + a2];
+        dh[r] = fma(sa.x, w0, dh[r]);
+        dh[r] = fma(sa.y, w1, dh[r]);
+        accW[2 * a2] = fma(sa.x, x[r], accW[2 * a2]);
+        accW[2 * a2 + 1] = fma(sa.y, x[r], accW[2 * a2 + 1]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      const double dzv = (zb[r] > 0.0) ? dh[r] : 0.0;
+      if (i + r < N) {
+        accz += dzv;
+        if (dz && c < H) dz[(i + r) * H + c] = dzv;
+      }
+    }
+  }
+  const int64_t m = (int64_t)A * H + A + H;
+  double* rec = part + (int64_t)blockIdx.x * m;
+  if (c < H) {
+#pragma unroll
+    for (int a = 0; a < AP; ++a)
+      if (a < A) rec[(int64_t)a * H + c] = accW[a];
+    rec[(int64_t)A * H + A + c] = accz;
+  }
+  // db: every wave accumulated the same rows' components; wave 0 writes
+  if (w == 0 && l < A) rec[(int64_t)A * H + l] = accb;
+}
+
+struct ScatterMean {
+  int AH, A;
+  double *dWm, *dbm, *dbz;
+  __device__ void operator()(int64_t e, double t) const {
+    if (e < AH)
+      dWm[e] = t;
+    else if (e < AH + A)
+      dbm[e - AH] = t;
+    else if (dbz)
+      dbz[e - AH - A] = t;
+  }
+};
+
+// mean_bwd_kernel blocks (partial records): 8 rows per block at least, 512 blocks at most
+static int grid_mean_bwd(int64_t N) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(512, (N + 7) / 8));
+}
+
+// one record [dW (A*H) | db (A) | dbz (H)] per block, then sum_records' group sums
+static size_t mean_ws_bytes(int64_t n, int hidden, int a_dim) {
+  const size_t m = (size_t)a_dim * (hidden + 1) + hidden;
+  return sum_records_bytes<kRedGroups>(grid_mean_bwd(std::max<int64_t>(n, 1)), m);
+}
+
 }  // namespace head
 }  // namespace mepol
 
@@ -585,4 +768,93 @@ extern "C" int mepol_head_backward_phase(const double* grad_logp, const double* 
   }
   return head_backward(grad_logp, z, n, hidden, bz, Wm, log_std, act, mu, a_dim, dz, dWm, dbm,
                        dlog_std, dbz, workspace, workspace_bytes, phase, stream);
+}
+
+// Mean-layer tangent of the Fisher-vector product: c_out [n, a_dim] = scale[a] (t Wm^T +
+// relu(z + bz) dWm^T + dbm) for t, z [n, hidden] (z the last PRE-activation without its bias bz,
+// nullable), Wm, dWm [a_dim, hidden], dbm, scale [a_dim] (device).
+extern "C" int mepol_mean_tangent(const double* t, const double* z, int64_t n, int hidden,
+                                  const double* bz, const double* Wm, const double* dWm,
+                                  const double* dbm, const double* scale, int a_dim,
+                                  double* c_out, void* stream) {
+  if (hidden <= 0 || a_dim <= 0 || !t || !z || !Wm || !dWm || !dbm || !scale || !c_out) {
+    set_error("mepol_mean_tangent: bad arguments (hidden, a_dim positive; t, z, Wm, dWm, dbm, "
+              "scale and c_out non-null)");
+    return kErrBadArg;
+  }
+  if (hidden > 64 * kMaxCols || a_dim > kMaxA) {
+    set_error("mepol_mean_tangent: hidden <= 512 and action_dim <= 32 only");
+    return kErrUnsupported;
+  }
+  if (n <= 0) return 0;
+  const int ap = a_dim <= 1 ? 1 : a_dim <= 2 ? 2 : a_dim <= 4 ? 4 : 8;
+  const int nch = (a_dim + ap - 1) / ap;
+  const int ncl = (hidden + 15) / 16;
+  const int64_t groups = (n + 3) / 4;
+  dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (groups + 3) / 4)), nch);
+  const size_t lds = ((size_t)2 * ncl * ap * 16 + (size_t)ncl * 16) * sizeof(double);
+  hipStream_t st = (hipStream_t)stream;
+#define MEPOL_MEAN_TAN(AP_)                                                                  \
+  if (ap == AP_) {                                                                           \
+    MEPOL_HIP(max_dynamic_lds<mean_tangent_kernel<AP_>>(72 * 1024));                         \
+    hipLaunchKernelGGL((mean_tangent_kernel<AP_>), g, dim3(256), lds, st, t, z, n, hidden,   \
+                       ncl, bz, Wm, dWm, dbm, scale, a_dim, c_out);                          \
+  }
+  MEPOL_MEAN_TAN(1) MEPOL_MEAN_TAN(2) MEPOL_MEAN_TAN(4) MEPOL_MEAN_TAN(8)
+#undef MEPOL_MEAN_TAN
+  MEPOL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mepol_mean_backward_workspace_size(int64_t n, int hidden, int a_dim,
+                                                  size_t* bytes) {
+  if (!bytes || hidden <= 0 || a_dim <= 0) {
+    set_error("mepol_mean_backward_workspace_size: bad arguments (hidden, a_dim positive; bytes "
+              "non-null)");
+    return kErrBadArg;
+  }
+  *bytes = mean_ws_bytes(n, hidden, a_dim);
+  return 0;
+}
+
+// Mean-layer backward from a cotangent c [n, a_dim] on mu: dWm [a_dim, hidden] = c^T relu(z + bz),
+// dbm [a_dim] = the column sums of c, dz [n, hidden] (nullable) = (c Wm) . [z + bz > 0] and dbz
+// [hidden] (nullable) = the column sums of dz; written, not accumulated.
+extern "C" int mepol_mean_backward(const double* c, const double* z, int64_t n, int hidden,
+                                   const double* bz, const double* Wm, int a_dim, double* dz,
+                                   double* dWm, double* dbm, double* dbz, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (hidden <= 0 || a_dim <= 0 || !c || !z || !Wm || !dWm || !dbm || !workspace) {
+    set_error("mepol_mean_backward: bad arguments (hidden, a_dim positive; c, z, Wm, dWm, dbm "
+              "and workspace non-null)");
+    return kErrBadArg;
+  }
+  if (hidden > 64 * kMaxCols || a_dim > kMaxA) {
+    set_error("mepol_mean_backward: hidden <= 512 and action_dim <= 32 only");
+    return kErrUnsupported;
+  }
+  if (n <= 0) return 0;
+  const int nb = grid_mean_bwd(n);
+  const size_t need = mean_ws_bytes(n, hidden, a_dim);
+  if (workspace_bytes < need) {
+    set_error("mepol_mean_backward: workspace %zu < %zu", workspace_bytes, need);
+    return kErrWorkspace;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double* part = (double*)workspace;
+  const int ap = a_dim <= 2 ? 2 : a_dim <= 4 ? 4 : a_dim <= 8 ? 8 : a_dim <= 16 ? 16 : 32;
+  const int hs = (hidden + 63) / 64 * 64;  // block width: one column per lane
+  const size_t lds = ((size_t)ap * hs + (size_t)(hs / 64) * 2 * ap) * sizeof(double);
+#define MEPOL_MEAN_BWD(AP_)                                                                   \
+  if (ap == AP_) {                                                                            \
+    MEPOL_HIP(max_dynamic_lds<mean_bwd_kernel<AP_>>(160 * 1024));                             \
+    hipLaunchKernelGGL((mean_bwd_kernel<AP_>), dim3(nb), dim3(hs), lds, st, c, z, n, hidden,  \
+                       hs, bz, Wm, a_dim, dz, part);                                          \
+  }
+  MEPOL_MEAN_BWD(2) MEPOL_MEAN_BWD(4) MEPOL_MEAN_BWD(8) MEPOL_MEAN_BWD(16) MEPOL_MEAN_BWD(32)
+#undef MEPOL_MEAN_BWD
+  MEPOL_CHECK_LAUNCH();
+  const int64_t m = (int64_t)a_dim * hidden + a_dim + hidden;
+  return sum_records<kRedGroups>(part, nb, m, ScatterMean{a_dim * hidden, a_dim, dWm, dbm, dbz},
+                                 st);
 }

@@ -64,6 +64,43 @@ __global__ __launch_bounds__(kThreads) void layer_fwd_kernel(const double* __res
   }
 }
 
+// Tangent of the layer along (dW, db): t = (x dW^T + db) . [h > 0], layer_fwd_kernel's mapping
+// with the lane's dW row in VGPRs and the forward's h read as the ReLU mask (relu'(0) = 0).
+template <int FP>
+__global__ __launch_bounds__(kThreads) void layer_tangent_kernel(const double* __restrict__ x,
+                                                                 int64_t N, int F,
+                                                                 const double* __restrict__ dW,
+                                                                 const double* __restrict__ db,
+                                                                 int H,
+                                                                 const double* __restrict__ h,
+                                                                 double* __restrict__ t) {
+  __shared__ double sx[kChunk][FP];
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c = blockIdx.y * 64 + l;
+  const bool col = c < H;
+  const int cc = col ? c : H - 1;  // clamped column: loads stay in bounds, results discarded
+  double wr[FP];
+#pragma unroll
+  for (int f = 0; f < FP; ++f) wr[f] = (col && f < F) ? dW[(int64_t)c * F + f] : 0.0;
+  const double bc = col ? db[c] : 0.0;
+  for (int e = threadIdx.x; e < kChunk * FP; e += kThreads) sx[e / FP][e % FP] = 0.0;
+  const int64_t step = (int64_t)gridDim.x * kChunk;
+  for (int64_t r0 = (int64_t)blockIdx.x * kChunk; r0 < N; r0 += step) {
+    const int nrow = (int)min<int64_t>(kChunk, N - r0);
+    __syncthreads();
+    stage_rows<FP>(x, F, nrow, r0, sx);
+    __syncthreads();
+#pragma unroll 1
+    for (int rr = w; rr < nrow; rr += 4) {
+      const double hv = h[(r0 + rr) * H + cc];
+      double acc = bc;
+#pragma unroll
+      for (int f = 0; f < FP; ++f) acc = fma(sx[rr][f], wr[f], acc);
+      if (col) t[(r0 + rr) * H + c] = hv > 0.0 ? acc : 0.0;
+    }
+  }
+}
+
 // part: [gridDim.x][H][F + 1]  (dW row c then db_c)
 template <int FP>
 __global__ __launch_bounds__(kThreads) void layer_bwd_kernel(const double* __restrict__ dh,
@@ -223,6 +260,29 @@ extern "C" int mepol_layer_forward(const double* x, int64_t n, int in_features, 
     const int gx = row_blocks(layer_fwd_kernel<FP>, n, gy);
     hipLaunchKernelGGL((layer_fwd_kernel<FP>), dim3(gx, gy), dim3(kThreads), 0, st, x, n,
                        in_features, W, b, out_features, h_out);
+  });
+  MEPOL_CHECK_LAUNCH();
+  return 0;
+}
+
+// t_out [n, out] = (x dW^T + db) . [h > 0]: the input layer's tangent along (dW [out, in],
+// db [out]) given the forward output h [n, out].
+extern "C" int mepol_layer_tangent(const double* x, int64_t n, int in_features, const double* dW,
+                                   const double* db, int out_features, const double* h,
+                                   double* t_out, void* stream) {
+  if (in_features <= 0 || in_features > 64 || out_features <= 0 || !x || !dW || !db || !h ||
+      !t_out) {
+    set_error("mepol_layer_tangent: bad arguments (0 < in_features <= 64, out_features > 0; x, "
+              "dW, db, h and t_out non-null)");
+    return kErrBadArg;
+  }
+  if (n <= 0) return 0;
+  const int gy = (out_features + 63) / 64;
+  hipStream_t st = (hipStream_t)stream;
+  MEPOL_FP_SWITCH(in_features, {
+    const int gx = row_blocks(layer_tangent_kernel<FP>, n, gy);
+    hipLaunchKernelGGL((layer_tangent_kernel<FP>), dim3(gx, gy), dim3(kThreads), 0, st, x, n,
+                       in_features, dW, db, out_features, h, t_out);
   });
   MEPOL_CHECK_LAUNCH();
   return 0;

@@ -520,6 +520,98 @@ def hidden_backward(dz_out, W, h_in, ws=None, dz_out_buf=None, db_out=None):
     return dz, db
 
 
+def _f64_rows(name, *ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError(f"{name} needs contiguous f64 tensors")
+
+
+def layer_tangent(x, dW, db, h, out=None):
+    """Tangent of the input layer h = relu(x W^T + b) along (dW, db): (x dW^T + db) * (h > 0)
+    (csrc/mlp.hip; in_features <= 64)."""
+    _require_device(x, dW, db, h, out)
+    n, f = x.shape
+    o = dW.shape[0]
+    if dW.shape != (o, f) or db.shape != (o,) or h.shape != (n, o):
+        raise ValueError("layer_tangent: x [n, in], dW [out, in], db [out], h [n, out]")
+    t = out if out is not None else torch.empty((n, o), dtype=torch.float64, device=x.device)
+    _f64_rows("layer_tangent", x, dW, db, h, t)
+    assert t.shape == (n, o)
+    call("mepol_layer_tangent", ptr(x), n, f, ptr(dW), ptr(db), o, ptr(h), ptr(t), _stream())
+    return t
+
+
+def hidden_tangent(t_in, h_in, W, dW, db, mask_src, mask_bias=None, out=None, variant=0):
+    """Tangent of a hidden layer h_out = relu(h_in W^T + b) along (dW, db) given the tangent t_in
+    of h_in: (t_in W^T + h_in dW^T + db) * (mask_src + mask_bias > 0) on the f64 matrix cores
+    (csrc/gemm.hip; both products in the same accumulators).  mask_src = h_out with no
+    mask_bias, or the pre-bias z with mask_bias = b.  `variant`: gemm_nt's tilings."""
+    _require_device(t_in, h_in, W, dW, db, mask_src, mask_bias, out)
+    n, k = t_in.shape
+    m = W.shape[0]
+    if (h_in.shape != (n, k) or W.shape != (m, k) or dW.shape != (m, k) or db.shape != (m,)
+            or mask_src.shape != (n, m) or (mask_bias is not None and mask_bias.shape != (m,))):
+        raise ValueError("hidden_tangent: t_in, h_in [n, k], W, dW [m, k], db [m], mask_src "
+                         "[n, m], mask_bias [m]")
+    t = out if out is not None else torch.empty((n, m), dtype=torch.float64, device=t_in.device)
+    _f64_rows("hidden_tangent", t_in, h_in, W, dW, db, mask_src, mask_bias, t)
+    assert t.shape == (n, m)
+    call("mepol_hidden_tangent", ptr(t_in), ptr(h_in), n, k, ptr(W), ptr(dW), ptr(db), m,
+         ptr(mask_src), ptr(mask_bias), ptr(t), int(variant), _stream())
+    return t
+
+
+def mean_tangent(t, z, Wm, dWm, dbm, scale, bz=None, out=None):
+    """c = scale * (t Wm^T + relu(z + bz) dWm^T + dbm): the mean layer's tangent along (tangent t
+    of the last hidden layer, dWm, dbm), scaled per action by the device vector `scale`
+    (csrc/head.hip; hidden <= 512, action_dim <= 32)."""
+    _require_device(t, z, Wm, dWm, dbm, scale, bz, out)
+    n, h = z.shape
+    a = Wm.shape[0]
+    if (t.shape != (n, h) or Wm.shape != (a, h) or dWm.shape != (a, h) or dbm.shape != (a,)
+            or scale.shape != (a,) or (bz is not None and bz.shape != (h,))):
+        raise ValueError("mean_tangent: t, z [n, hidden], Wm, dWm [a, hidden], dbm, scale [a], "
+                         "bz [hidden]")
+    c = out if out is not None else torch.empty((n, a), dtype=torch.float64, device=z.device)
+    _f64_rows("mean_tangent", t, z, Wm, dWm, dbm, scale, bz, c)
+    assert c.shape == (n, a)
+    call("mepol_mean_tangent", ptr(t), ptr(z), n, h, ptr(bz), ptr(Wm), ptr(dWm), ptr(dbm),
+         ptr(scale), a, ptr(c), _stream())
+    return c
+
+
+def mean_backward_workspace(n, hidden, a, device):
+    """A caller-owned scratch buffer for mean_backward at these sizes."""
+    return _own_workspace(device, "mean_backward", n, hidden, a)
+
+
+def mean_backward(c, z, Wm, bz=None, need_dz=True, ws=None, dz_out=None, outs=None):
+    """Mean-layer backward from a cotangent c [n, a] on mu: returns (dz or None, dWm, dbm, dbz or
+    None) with dWm = c^T relu(z + bz), dbm = c.sum(0), dz = (c Wm) * (z + bz > 0), dbz = dz.sum(0)
+    (csrc/head.hip; fixed-order row sums).  `outs`: optional (dWm, dbm, dbz) tensors to write;
+    `dz_out`: optional dz buffer."""
+    _require_device(c, z, Wm, bz, dz_out)
+    n, h = z.shape
+    a = Wm.shape[0]
+    if c.shape != (n, a) or Wm.shape != (a, h) or (bz is not None and bz.shape != (h,)):
+        raise ValueError("mean_backward: c [n, a], z [n, hidden], Wm [a, hidden], bz [hidden]")
+    dev = z.device
+    ws = _ws_or_cached(ws, dev, "meanbwd", "mean_backward", n, h, a)
+    dz = (dz_out if dz_out is not None else torch.empty_like(z)) if need_dz else None
+    if outs is not None:
+        dWm, dbm, dbz = outs
+    else:
+        dWm = torch.empty((a, h), dtype=torch.float64, device=dev)
+        dbm = torch.empty(a, dtype=torch.float64, device=dev)
+        dbz = torch.empty(h, dtype=torch.float64, device=dev) if bz is not None else None
+    _f64_rows("mean_backward", c, z, Wm, bz, dz, dWm, dbm, dbz)
+    assert dWm.shape == (a, h) and dbm.numel() == a and (dbz is None or dbz.numel() == h)
+    assert dz is None or dz.shape == (n, h)
+    call("mepol_mean_backward", ptr(c), ptr(z), n, h, ptr(bz), ptr(Wm), a, ptr(dz), ptr(dWm),
+         ptr(dbm), ptr(dbz), ptr(ws), ws.numel(), _stream())
+    return dz, dWm, dbm, dbz
+
+
 GEMM_NT_CUS = 256          # gfx950
 GEMM_NT_KEEP_ROWS = 16384  # from here on variant 0 always (the large-batch path, as measured)
 
@@ -554,14 +646,17 @@ def layer_forward(x, W, b, out=None):
     return h
 
 
-def layer_backward(dh, h, x, ws=None):
+def layer_backward(dh, h, x, ws=None, dW_out=None, db_out=None):
     """(dW, db) of h = relu(x W^T + b) from dL/dh and the forward output h.  `ws`: caller-owned
-    scratch (layer_workspace); default: the per-stream eager cache."""
+    scratch (layer_workspace); default: the per-stream eager cache.  `dW_out` / `db_out`:
+    optional contiguous tensors the results are written into."""
     n, f = x.shape
     out = h.shape[1]
     ws = _ws_or_cached(ws, x.device, "layer", "layer", n, f, out)
-    dW = torch.empty((out, f), dtype=torch.float64, device=x.device)
-    db = torch.empty(out, dtype=torch.float64, device=x.device)
+    dW = dW_out if dW_out is not None else torch.empty((out, f), dtype=torch.float64,
+                                                      device=x.device)
+    db = db_out if db_out is not None else torch.empty(out, dtype=torch.float64, device=x.device)
+    assert dW.is_contiguous() and dW.shape == (out, f) and db.is_contiguous() and db.numel() == out
     call("mepol_layer_backward", ptr(dh), ptr(h), ptr(x), n, f, out, ptr(dW), ptr(db), ptr(ws),
          ws.numel(), _stream())
     return dW, db

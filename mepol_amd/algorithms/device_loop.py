@@ -36,10 +36,10 @@ import os
 import weakref
 
 import torch
-import torch.nn as nn
 
-from .. import ops
-from ..policy import GaussianPolicy, multilayer_ok
+from .. import kernel_path, ops
+from ..kernel_path import linear_layers
+from ..policy import GaussianPolicy
 
 _ADAM, _RMSPROP = 0, 1
 
@@ -63,9 +63,14 @@ def _opt_kind(optimizer):
     return None
 
 
-def _supported(batch, behavioral_policy, target_policy, optimizer, min_rows, shape_ok):
-    """The conditions every graph iteration shares; shape_ok(hidden widths, input features) is the
-    caller's condition on the network."""
+def _network_kind(policy):
+    return kernel_path.network_kind([m.out_features for m in linear_layers(policy)],
+                                    policy.num_features)
+
+
+def _supported(batch, behavioral_policy, target_policy, optimizer, min_rows, kind):
+    """The conditions every graph iteration shares; kind is the kernel_path.network_kind the
+    caller's iteration runs."""
     if os.environ.get("MEPOL_DEVICE_LOOP", "1") == "0":
         return False
     if not isinstance(target_policy, GaussianPolicy) or target_policy is behavioral_policy:
@@ -74,11 +79,10 @@ def _supported(batch, behavioral_policy, target_policy, optimizer, min_rows, sha
         return False
     if not target_policy._fused_head_ok(batch.states_flat, batch.actions_flat, min_rows):
         return False
-    layers = [m for m in target_policy.net if isinstance(m, nn.Linear)]
-    if not shape_ok([m.out_features for m in layers], target_policy.num_features):
+    if _network_kind(target_policy) != kind:
         return False
     params = list(target_policy.parameters())
-    if len(params) != 2 * len(layers) + 3 or any(
+    if len(params) != 2 * len(linear_layers(target_policy)) + 3 or any(
             p.dtype != torch.float64 or not p.is_contiguous() or p.device != batch.device
             for p in params):
         return False
@@ -93,7 +97,7 @@ def supported(batch, behavioral_policy, target_policy, optimizer, min_rows=None)
     exactly the target's parameters.  min_rows: the caller's own batch floor instead of
     policy.fused_min_rows() (the sharded iteration keeps 16384 rows per rank)."""
     return _supported(batch, behavioral_policy, target_policy, optimizer, min_rows,
-                      lambda widths, nf: len(widths) == 2 and nf <= 64)
+                      kernel_path.TWO_LAYER)
 
 
 def supported_multilayer(batch, behavioral_policy, target_policy, optimizer):
@@ -101,7 +105,8 @@ def supported_multilayer(batch, behavioral_policy, target_policy, optimizer):
     layers, which MultiLayerIteration runs (policy.multilayer_ok: the shapes _MultiLayerLogp
     takes).  supported() itself stays False for them: the sharded iteration (parallel.py) asks
     it and is written for the two-layer parameter list."""
-    return _supported(batch, behavioral_policy, target_policy, optimizer, None, multilayer_ok)
+    return _supported(batch, behavioral_policy, target_policy, optimizer, None,
+                      kernel_path.MULTILAYER)
 
 
 _guard_depth, _guard_restore = 0, False
@@ -203,7 +208,7 @@ class DeviceIteration:
         """self.named (the parameters in the order _backward returns their gradients) and what
         forward / _backward need beyond the shared inputs: here the two-layer activations, the
         fused kernels' switches and buffers, the workspaces and the dh1 stream."""
-        l1, l2 = [m for m in target_policy.net if isinstance(m, nn.Linear)]
+        l1, l2 = linear_layers(target_policy)
         self.named = (l1.weight, l1.bias, l2.weight, l2.bias, target_policy.mean.weight,
                       target_policy.mean.bias, target_policy.log_std)
         W1, _, W2, _, _, _, _ = self.named
@@ -585,7 +590,7 @@ class MultiLayerIteration(DeviceIteration):
     same replay machinery (scalar blocks, shadows, speculative second graph, cancel); the
     network part is _MultiLayerLogp's kernel sequence on static per-layer buffers:
 
-        forward   layer_forward -> gemm_nt (bias + ReLU) x (L - 2) -> gemm_nt (z_L) -> head
+        forward   kernel_path.hidden_forward (layer_forward -> gemm_nt x (L - 1)) -> head
         backward  head row kernel -> hidden_backward x (L - 1) -> layer_backward  (one chain)
                   weight_grad x (L - 1), the head's reduces                       (forked stream)
 
@@ -595,11 +600,12 @@ class MultiLayerIteration(DeviceIteration):
     the body are DeviceIteration's; only _alloc_network, forward and _backward are replaced."""
 
     def _alloc_network(self, target_policy, batch):
-        layers = [m for m in target_policy.net if isinstance(m, nn.Linear)]
+        layers = linear_layers(target_policy)
         L = self.L = len(layers)
         # (W_1, b_1, ..., W_L, b_L, Wm, bm, log_std): the order _backward returns gradients in
         self.named = tuple(t for m in layers for t in (m.weight, m.bias)) + (
             target_policy.mean.weight, target_policy.mean.bias, target_policy.log_std)
+        self.Ws, self.bs = self.named[0:2 * L:2], self.named[1:2 * L:2]
         N, dev = self.N, self.device
         f64 = dict(dtype=torch.float64, device=dev)
         widths = [m.out_features for m in layers]
@@ -616,24 +622,16 @@ class MultiLayerIteration(DeviceIteration):
 
     @torch.no_grad()
     def forward(self):
-        L = self.L
-        Ws, bs = self.named[0:2 * L:2], self.named[1:2 * L:2]
-        Wm, bm, ls = self.named[2 * L:]
-        ops.layer_forward(self.x, Ws[0], bs[0], out=self.hs[0])
-        for l in range(1, L - 1):
-            ops.gemm_nt(self.hs[l - 1], Ws[l], bias=bs[l], relu=True, out=self.hs[l],
-                        variant=ops.gemm_nt_variant(self.N, Ws[l].shape[0]))
-        ops.gemm_nt(self.hs[L - 2], Ws[L - 1], out=self.zL,
-                    variant=ops.gemm_nt_variant(self.N, Ws[L - 1].shape[0]))
-        ops.head_forward(self.zL, Wm, bm, ls, self.act, bz=bs[L - 1], mu_out=self.mu,
+        Wm, bm, ls = self.named[-3:]
+        kernel_path.hidden_forward(self.x, self.Ws, self.bs, hs_out=self.hs, z_out=self.zL)
+        ops.head_forward(self.zL, Wm, bm, ls, self.act, bz=self.bs[-1], mu_out=self.mu,
                          logp_out=self.logp)
 
     def _backward(self, grad):
         """(dW_1, db_1, ..., dW_L, db_L, dWm, dbm, dls) from dH/dlogp: the _MultiLayerLogp
         backward.  Index l below is 0-based (Ws[l] = W_{l+1}, hs[l] = h_{l+1})."""
-        L = self.L
-        Ws, bs = self.named[0:2 * L:2], self.named[1:2 * L:2]
-        Wm, _, ls = self.named[2 * L:]
+        L, Ws, bs = self.L, self.Ws, self.bs
+        Wm, _, ls = self.named[-3:]
         cur = torch.cuda.current_stream()
         self.fork.wait_stream(cur)
         dzL, dWm, dbm, dls, dbL, head_reduce = ops.head_backward(
@@ -678,7 +676,7 @@ def get(target_policy, optimizer, batch, k, G, B, ns, eps):
     if it is None or not it.matches(target_policy, optimizer, batch, k, G, B, ns, eps):
         it = None  # drop the old graph and buffers before allocating new ones
         _CACHE.pop(target_policy, None)
-        deep = sum(isinstance(m, nn.Linear) for m in target_policy.net) > 2
+        deep = _network_kind(target_policy) == kernel_path.MULTILAYER
         cls = MultiLayerIteration if deep else DeviceIteration
         it = cls(target_policy, optimizer, batch, k, G, B, ns, eps)
         _CACHE[target_policy] = it

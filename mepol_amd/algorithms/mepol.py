@@ -19,7 +19,6 @@ Differences a caller can observe (all documented in DESIGN.md):
     reference's random stream (dynamics are; see tests/test_gpu_envs.py).
 """
 import atexit
-import math
 import os
 import time
 import weakref
@@ -29,8 +28,9 @@ import scipy.special
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import kernel_path, ops
 from ..envs.wrappers import unwrap
+from ..kernel_path import linear_layers
 from . import particles as P
 
 float_type = torch.float64
@@ -54,10 +54,10 @@ class _RolloutGraph:
     and replayed every epoch; the policy's parameters are read in place, so load_state_dict
     between epochs needs no re-capture."""
 
-    def __init__(self, policy, env_id, init, T, a_dim, nf):
+    def __init__(self, key, policy, env_id, init, T, a_dim, nf):
         dev = init.device
         n = init.shape[0]
-        self.key = (env_id, n, T, a_dim, nf, tuple(p.data_ptr() for p in policy.parameters()))
+        self.key = key  # _rollout_graph's: what this capture is valid for
         self.init = init.clone()
         self.noise = torch.zeros((T, n, a_dim), dtype=torch.float64, device=dev)
         self.states = torch.zeros((n, T + 1, nf), dtype=torch.float32, device=dev)
@@ -134,23 +134,8 @@ def _rollout_graph(policy, env_id, init, T, a_dim, nf):
     if g is None:
         if len(per) >= 4:  # bounded: the epoch and full-entropy shapes of a run
             per.clear()
-        g = per[key] = _RolloutGraph(policy, env_id, init, T, a_dim, nf)
+        g = per[key] = _RolloutGraph(key, policy, env_id, init, T, a_dim, nf)
     return g
-
-
-def _rollout_mlp_layers(policy, nf, a_dim):
-    """((W1, b1), (W2, b2)) when the policy is the reference's nf = 2 -> [h0, h1] -> a ReLU MLP in
-    f64 that the one-launch rollout kernel covers (h <= 512, a <= 8); else None."""
-    if os.environ.get("MEPOL_ROLLOUT_FUSED", "1") == "0" or nf != 2 or a_dim > 8:
-        return None
-    if getattr(policy, "activation", None) is not nn.ReLU:
-        return None
-    layers = [m for m in policy.net if isinstance(m, nn.Linear)]
-    if len(layers) != 2 or any(m.weight.dtype != torch.float64 for m in layers):
-        return None
-    if layers[0].in_features != 2 or max(m.out_features for m in layers) > 512:
-        return None
-    return tuple((m.weight.detach(), m.bias.detach()) for m in layers)
 
 
 # Weight words of layers 2 .. L (sum of h_{l-1} h_l) up to which the deep rollout kernel beat the
@@ -160,25 +145,39 @@ def _rollout_mlp_layers(policy, nf, a_dim):
 ROLLOUT_DEEP_MAX_WORDS = 2 * 512 * 512
 
 
-def _rollout_deep_layers(policy, nf, a_dim):
-    """[(W1, b1), ..., (W_L, b_L)] when the policy is an nf = 2 -> [h_1 .. h_L] -> a ReLU MLP in
-    f64 with 3 to 6 hidden layers that the deep one-launch rollout kernel covers (h <= 512, odd
-    widths included, a <= 8; csrc/rollout_deep.hip) and is measured to be faster for (at most
-    ROLLOUT_DEEP_MAX_WORDS weight words behind layer 1); else None.  Two hidden layers are
-    _rollout_mlp_layers'."""
-    if os.environ.get("MEPOL_ROLLOUT_FUSED", "1") == "0" or nf != 2 or a_dim > 8:
+def _rollout_layers(policy, nf, a_dim, deep):
+    """[(W_1, b_1), ..., (W_L, b_L)] when a one-launch rollout kernel covers the policy, an
+    nf = 2 -> [h_1 .. h_L] -> a ReLU MLP in f64 with h <= 512 (odd widths included) and a <= 8,
+    else None.  L = 2 (csrc/envs.hip), or with deep L = 3 to 6 (csrc/rollout_deep.hip) and at most
+    ROLLOUT_DEEP_MAX_WORDS weight words behind layer 1: where that kernel is the faster one."""
+    if (os.environ.get("MEPOL_ROLLOUT_FUSED", "1") == "0" or nf != kernel_path.ROLLOUT_FEATURES
+            or a_dim > kernel_path.ROLLOUT_MAX_ACTIONS):
         return None
     if getattr(policy, "activation", None) is not nn.ReLU:
         return None
-    layers = [m for m in policy.net if isinstance(m, nn.Linear)]
-    if not 3 <= len(layers) <= 6 or any(m.weight.dtype != torch.float64 for m in layers):
+    layers = linear_layers(policy)
+    lo, hi = (kernel_path.MULTILAYER_MIN, kernel_path.MULTILAYER_MAX) if deep else (2, 2)
+    if not lo <= len(layers) <= hi or any(m.weight.dtype != torch.float64 for m in layers):
         return None
-    if layers[0].in_features != 2 or max(m.out_features for m in layers) > 512:
+    if (layers[0].in_features != kernel_path.ROLLOUT_FEATURES
+            or max(m.out_features for m in layers) > kernel_path.ROLLOUT_MAX_WIDTH):
         return None
-    cap = int(os.environ.get("MEPOL_ROLLOUT_DEEP_MAX_WORDS", ROLLOUT_DEEP_MAX_WORDS))
-    if sum(m.in_features * m.out_features for m in layers[1:]) > cap:
-        return None
+    if deep:
+        cap = int(os.environ.get("MEPOL_ROLLOUT_DEEP_MAX_WORDS", ROLLOUT_DEEP_MAX_WORDS))
+        if sum(m.in_features * m.out_features for m in layers[1:]) > cap:
+            return None
     return [(m.weight.detach(), m.bias.detach()) for m in layers]
+
+
+def _rollout_mlp_layers(policy, nf, a_dim):
+    """((W1, b1), (W2, b2)) of the reference's two-layer policy as _rollout_layers takes it."""
+    layers = _rollout_layers(policy, nf, a_dim, deep=False)
+    return None if layers is None else tuple(layers)
+
+
+def _rollout_deep_layers(policy, nf, a_dim):
+    """[(W1, b1), ..., (W_L, b_L)] of 3 to 6 hidden layers as _rollout_layers takes them."""
+    return _rollout_layers(policy, nf, a_dim, deep=True)
 
 
 def collect_particles_device(env, policy, num_traj, traj_len, state_filter, generator=None,
@@ -216,68 +215,75 @@ def collect_particles_device(env, policy, num_traj, traj_len, state_filter, gene
     actions = torch.zeros((num_traj, T, a_dim), dtype=torch.float32, device=dev)
     with torch.no_grad():
         if kind in ("mountaincar", "gridworld"):
-            env_id = 0 if kind == "mountaincar" else 1
-            init = base.reset_batch_torch(total, dev, generator)[lo:hi]
-            noise_all = torch.randn((T, total, a_dim), dtype=torch.float64, device=dev,
-                                    generator=generator)
-            lin = _rollout_mlp_layers(policy, nf, a_dim)
-            deep = _rollout_deep_layers(policy, nf, a_dim) if lin is None else None
-            if lin is not None or deep is not None:
-                # all T steps in one launch (csrc/envs.hip rollout_mlp_kernel, or
-                # csrc/rollout_deep.hip for 3 to 6 hidden layers)
-                head = (policy.mean.weight.detach(), policy.mean.bias.detach(),
-                        policy.log_std.detach(), init, noise_all[:, lo:hi], states, actions,
-                        visited)
-                if lin is not None:
-                    (W1, b1), (W2, b2) = lin
-                    ops.rollout_mlp(env_id, W1, b1, W2, b2, *head)
-                else:
-                    ops.rollout_deep(env_id, deep, *head)
-                rtl = torch.full((num_traj, 1), T, dtype=torch.int32, device=dev)
-                next_states = states[:, 1:, :].reshape(-1, nf)
-                if state_filter is not None:
-                    next_states = next_states[:, list(state_filter)]
-                return states, actions, rtl, next_states.contiguous()
-            graph = _rollout_graph(policy, env_id, init, T, a_dim, nf) if visited is None else None
-            if graph is not None:
-                states, actions = graph.run(init, noise_all[:, lo:hi])
-                rtl = torch.full((num_traj, 1), T, dtype=torch.int32, device=dev)
-                next_states = states[:, 1:, :].reshape(-1, nf)
-                if state_filter is not None:
-                    next_states = next_states[:, list(state_filter)]
-                return states, actions, rtl, next_states.contiguous()
-            env64 = init.clone() if env_id == 0 else None
-            env32 = init.clone() if env_id == 1 else None
-            policy_in = init.to(torch.float64).contiguous()
-            states[:, 0] = init.to(torch.float32)
-            log_std = policy.log_std.detach().contiguous()
-            for t in range(T):
-                mean = policy.mean_action(policy_in).contiguous()
-                noise = noise_all[t, lo:hi]
-                ops.rollout_step(env_id, env64, env32, mean, noise, log_std, t, T, states, actions,
-                                 policy_in)
-                if visited is not None:
-                    visited[:, t].copy_(policy_in)
+            states, actions = _rollout_hip_stepped(0 if kind == "mountaincar" else 1, base, policy,
+                                                   total, lo, hi, generator, visited, states,
+                                                   actions)
+        elif world > 1:
+            raise NotImplementedError("sharded rollouts need a batched (HIP-stepped) env")
         else:
-            if world > 1:
-                raise NotImplementedError("sharded rollouts need a batched (HIP-stepped) env")
-            envs = [env] + [_clone_env(env) for _ in range(num_traj - 1)]
-            s = np.stack([e.reset() for e in envs])
-            states[:, 0] = torch.as_tensor(s, dtype=torch.float32, device=dev)
-            for t in range(T):
-                x = torch.as_tensor(s, dtype=torch.float64, device=dev)
-                _, a = policy(x)
-                actions[:, t] = a.to(torch.float32)
-                a_np = a.cpu().numpy()
-                s = np.stack([e.step(a_np[i])[0] for i, e in enumerate(envs)])
-                states[:, t + 1] = torch.as_tensor(s, dtype=torch.float32, device=dev)
-                if visited is not None:
-                    visited[:, t] = torch.as_tensor(s, dtype=torch.float64, device=dev)
+            _rollout_host_stepped(env, policy, visited, states, actions)
     rtl = torch.full((num_traj, 1), T, dtype=torch.int32, device=dev)
     next_states = states[:, 1:, :].reshape(-1, nf)
     if state_filter is not None:
         next_states = next_states[:, list(state_filter)]
     return states, actions, rtl, next_states.contiguous()
+
+
+def _rollout_hip_stepped(env_id, base, policy, total, lo, hi, generator, visited, states, actions):
+    """Trajectories [lo, hi) of `total` on a HIP-stepped env (0 MountainCar, 1 GridWorld) by the
+    first route that takes the policy: the two-layer one-launch kernel, the deep one, the replayed
+    per-step graph (not with `visited`), the eager per-step loop.  All `total` initial states, then
+    all the noise, are drawn first.  Returns the given tensors filled, or the graph's copies."""
+    dev = states.device
+    _, T, a_dim = actions.shape
+    nf = states.shape[2]
+    init = base.reset_batch_torch(total, dev, generator)[lo:hi]
+    noise = torch.randn((T, total, a_dim), dtype=torch.float64, device=dev,
+                        generator=generator)[:, lo:hi]
+    layers = _rollout_mlp_layers(policy, nf, a_dim) or _rollout_deep_layers(policy, nf, a_dim)
+    if layers:
+        # all T steps in one launch (csrc/envs.hip rollout_mlp_kernel, or csrc/rollout_deep.hip
+        # for 3 to 6 hidden layers)
+        head = (policy.mean.weight.detach(), policy.mean.bias.detach(), policy.log_std.detach(),
+                init, noise, states, actions, visited)
+        if len(layers) == 2:
+            ops.rollout_mlp(env_id, *layers[0], *layers[1], *head)
+        else:
+            ops.rollout_deep(env_id, layers, *head)
+        return states, actions
+    graph = _rollout_graph(policy, env_id, init, T, a_dim, nf) if visited is None else None
+    if graph is not None:
+        return graph.run(init, noise)
+    env64 = init.clone() if env_id == 0 else None
+    env32 = init.clone() if env_id == 1 else None
+    policy_in = init.to(torch.float64).contiguous()
+    states[:, 0] = init.to(torch.float32)
+    log_std = policy.log_std.detach().contiguous()
+    for t in range(T):
+        mean = policy.mean_action(policy_in).contiguous()
+        ops.rollout_step(env_id, env64, env32, mean, noise[t], log_std, t, T, states, actions,
+                         policy_in)
+        if visited is not None:
+            visited[:, t].copy_(policy_in)
+    return states, actions
+
+
+def _rollout_host_stepped(env, policy, visited, states, actions):
+    """Fills states / actions from copies of `env` stepped on the host, one policy call per step."""
+    dev = states.device
+    num_traj, T, _ = actions.shape
+    envs = [env] + [_clone_env(env) for _ in range(num_traj - 1)]
+    s = np.stack([e.reset() for e in envs])
+    states[:, 0] = torch.as_tensor(s, dtype=torch.float32, device=dev)
+    for t in range(T):
+        x = torch.as_tensor(s, dtype=torch.float64, device=dev)
+        _, a = policy(x)
+        actions[:, t] = a.to(torch.float32)
+        a_np = a.cpu().numpy()
+        s = np.stack([e.step(a_np[i])[0] for i, e in enumerate(envs)])
+        states[:, t + 1] = torch.as_tensor(s, dtype=torch.float32, device=dev)
+        if visited is not None:
+            visited[:, t] = torch.as_tensor(s, dtype=torch.float64, device=dev)
 
 
 def get_heatmap(env, policy, discretizer, num_episodes, num_steps, cmap, interp, labels):

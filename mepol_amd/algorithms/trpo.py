@@ -28,8 +28,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import kernel_path, ops
 from .. import policy as _policy
+from ..kernel_path import linear_layers
 
 KL_VAR_EPS = 1e-7  # the epsilon on the variance in the reference's KL (trpo.py:384)
 
@@ -38,10 +39,10 @@ KL_VAR_EPS = 1e-7  # the epsilon on the variance in the reference's KL (trpo.py:
 # the double backward for both policies ("TRPO policy step").
 FVP_MIN_ROWS = _policy.FUSED_MIN_ROWS
 
-FVP_MIN_LAYERS, FVP_MAX_LAYERS = 2, 6
-FVP_MAX_WIDTH = 512
-FVP_MAX_FEATURES = 64
-FVP_MAX_ACTIONS = 32
+FVP_MIN_LAYERS, FVP_MAX_LAYERS = 2, kernel_path.MULTILAYER_MAX
+FVP_MAX_WIDTH = kernel_path.HEAD_MAX_WIDTH  # of EVERY hidden layer, not only the head's input
+FVP_MAX_FEATURES = kernel_path.MAX_FEATURES
+FVP_MAX_ACTIONS = kernel_path.HEAD_MAX_ACTIONS
 
 
 def fvp_min_rows():
@@ -49,15 +50,11 @@ def fvp_min_rows():
     return int(v) if v else FVP_MIN_ROWS
 
 
-def _linear_layers(policy):
-    return [m for m in policy.net if isinstance(m, nn.Linear)]
-
-
 def fvp_kernels_ok(policy, states):
     """True when PolicyFisher (and the constraint's mean) take the HIP kernels: an f64 ReLU policy
     on the GPU with 2 to 6 hidden layers of even width <= 512, at most 64 features and 32
     actions, and a batch of at least fvp_min_rows() rows."""
-    layers = _linear_layers(policy)
+    layers = linear_layers(policy)
     return (states.is_cuda and states.dim() == 2 and states.dtype == torch.float64
             and policy.log_std.is_cuda and policy.log_std.dtype == torch.float64
             and policy.activation is nn.ReLU
@@ -72,8 +69,8 @@ def plain_mean(policy, states):
     """mu(states) restated with F.linear and the policy's activation modules: twice
     differentiable in every parameter at any batch size."""
     h = states
-    for m in policy.net:
-        h = F.linear(h, m.weight, m.bias) if isinstance(m, nn.Linear) else m(h)
+    for layer in policy.net:
+        h = F.linear(h, layer.weight, layer.bias) if isinstance(layer, nn.Linear) else layer(h)
     return F.linear(h, policy.mean.weight, policy.mean.bias)
 
 
@@ -85,29 +82,17 @@ def gaussian_kl(mu0, log_std0, mu1, log_std1):
             + log_std1 - log_std0).sum(dim=1).mean()
 
 
-def _kernel_forward(x, Ws, bs):
-    """(h_1 .. h_{L-1}, z_L) of the hidden layers on the forward kernels: z_L is the last
-    pre-activation WITHOUT its bias, as the head kernels take it."""
-    n, L = x.shape[0], len(Ws)
-    hs = [ops.layer_forward(x, Ws[0], bs[0])]
-    for l in range(1, L - 1):
-        hs.append(ops.gemm_nt(hs[-1], Ws[l], bias=bs[l], relu=True,
-                              variant=ops.gemm_nt_variant(n, Ws[l].shape[0])))
-    zL = ops.gemm_nt(hs[-1], Ws[L - 1], variant=ops.gemm_nt_variant(n, Ws[L - 1].shape[0]))
-    return hs, zL
-
-
 def policy_mean(policy, states, actions=None):
-    """mu(states) without a graph: the forward kernels (ops.layer_forward, ops.gemm_nt,
+    """mu(states) without a graph: the forward kernels (kernel_path.hidden_forward,
     ops.head_forward) where fvp_kernels_ok, the policy's own mean_action otherwise."""
     with torch.no_grad():
         if not fvp_kernels_ok(policy, states):
             return policy.mean_action(states)
-        layers = _linear_layers(policy)
+        layers = linear_layers(policy)
         x = states.contiguous()
         Ws = [m.weight.detach().contiguous() for m in layers]
         bs = [m.bias.detach().contiguous() for m in layers]
-        _, zL = _kernel_forward(x, Ws, bs)
+        _, zL = kernel_path.hidden_forward(x, Ws, bs)
         if actions is None:
             actions = torch.zeros((x.shape[0], policy.action_dim), dtype=torch.float64,
                                   device=x.device)
@@ -149,7 +134,7 @@ class PolicyFisher:
         dev = states.device
         x = states.detach().contiguous()
         n = x.shape[0]
-        layers = _linear_layers(policy)
+        layers = linear_layers(policy)
         L = len(layers)
         self.x, self.n, self.L = x, n, L
         self.Ws = [m.weight.detach().clone().contiguous() for m in layers]
@@ -160,7 +145,7 @@ class PolicyFisher:
         a = self.Wm.shape[0]
         f64 = dict(dtype=torch.float64, device=dev)
         with torch.no_grad():
-            self.hs, self.zL = _kernel_forward(x, self.Ws, self.bs)
+            self.hs, self.zL = kernel_path.hidden_forward(x, self.Ws, self.bs)
             self.mu0, _ = ops.head_forward(self.zL, self.Wm, self.bm, self.log_std0,
                                            torch.zeros((n, a), **f64), bz=self.bs[-1])
             u = torch.exp(2.0 * self.log_std0)
@@ -204,6 +189,12 @@ class PolicyFisher:
         self._ws_hb = [None] + [ops.hidden_backward_workspace(n, widths[l - 1], dev)
                                 for l in range(1, L)]
         self._ws_layer = ops.layer_workspace(n, x.shape[1], widths[0], dev)
+        # kernel_path.hidden_backward's outputs: dW_l and db_l into the result, dz_l over t_l
+        self._backward_out = dict(
+            dW_out=[self._vout["W", l] for l in range(L)],
+            db_out=[self._vout["b", l] for l in range(L - 1)], dz_out=self._act,
+            ws_wgrad=self._ws_wg, ws_hidden=self._ws_hb, ws_layer=self._ws_layer,
+            layer_db_out=self._db_unused)
 
     def _hvp_kernels(self, v):
         L, vin, out = self.L, self._vin, self._vout
@@ -222,12 +213,7 @@ class PolicyFisher:
         dz, _, _, _ = ops.mean_backward(c, self.zL, self.Wm, bz=self.bs[-1], ws=self._ws_mean,
                                         dz_out=self._act[L - 1],
                                         outs=(out["Wm", 0], out["bm", 0], out["b", L - 1]))
-        for l in range(L - 1, 0, -1):
-            ops.weight_grad(dz, self.hs[l - 1], out=out["W", l], ws=self._ws_wg[l])
-            dz, _ = ops.hidden_backward(dz, self.Ws[l], self.hs[l - 1], ws=self._ws_hb[l],
-                                        dz_out_buf=self._act[l - 1], db_out=out["b", l - 1])
-        ops.layer_backward(dz, self.hs[0], self.x, ws=self._ws_layer, dW_out=out["W", 0],
-                           db_out=self._db_unused)
+        kernel_path.hidden_backward(dz, self.x, self.Ws, self.hs, **self._backward_out)
         torch.mul(self.ls_coef, vin["ls", 0], out=out["ls", 0])
         res = torch.index_select(self._opad, 0, self._scatter)
         return res.add_(v, alpha=self.damping)

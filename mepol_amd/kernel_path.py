@@ -1,0 +1,75 @@
+"""What the Gaussian policy's HIP kernel path takes, and its layer chain, each written once for
+get_log_p (policy.py), the graph loop (algorithms/device_loop.py), TRPO's Fisher products
+(algorithms/trpo.py) and the one-launch rollouts (algorithms/mepol.py).  The gates stay with
+those consumers and add what only they know (row floors, dtypes, the optimizer)."""
+import torch.nn as nn
+
+from . import ops
+
+# Shape limits of the kernels; ops.py keeps the fused two-layer kernels' own (policy_forward_ok).
+MAX_FEATURES = 64                      # input layer: csrc/mlp.hip, csrc/policy_fwd.hip
+HEAD_MAX_WIDTH = 512                   # last hidden width of the fused head, csrc/head.hip
+HEAD_MAX_ACTIONS = 32
+MULTILAYER_MIN, MULTILAYER_MAX = 3, 6  # hidden layers of the deep chain (2 L + 3 <= 16 tensors)
+ROLLOUT_MAX_WIDTH = 512                # one-launch rollouts: csrc/envs.hip, csrc/rollout_deep.hip
+ROLLOUT_MAX_ACTIONS = 8
+ROLLOUT_FEATURES = 2
+
+TWO_LAYER, MULTILAYER = "two-layer", "multilayer"
+
+
+def linear_layers(policy):
+    """The policy's hidden Linear layers, in order (policy.net without its activations)."""
+    return [m for m in policy.net if isinstance(m, nn.Linear)]
+
+
+def network_kind(widths, num_features):
+    """The chain that runs hidden layers of these widths: TWO_LAYER (_TwoLayerLogp,
+    DeviceIteration), MULTILAYER (3 to 6 layers, all even: 16-B aligned weight rows for the
+    matrix-core kernels; hidden_forward / hidden_backward), or None (only the head's kernels)."""
+    if num_features > MAX_FEATURES:
+        return None
+    if len(widths) == 2:
+        return TWO_LAYER
+    if MULTILAYER_MIN <= len(widths) <= MULTILAYER_MAX and all(w % 2 == 0 for w in widths):
+        return MULTILAYER
+    return None
+
+
+def _at(seq, i):
+    return None if seq is None else seq[i]
+
+
+def hidden_forward(x, Ws, bs, hs_out=None, z_out=None):
+    """([h_1 .. h_{L-1}], z_L) of L >= 2 hidden layers: h_1 = relu(x W_1^T + b_1) (csrc/mlp.hip),
+    h_l = relu(h_{l-1} W_l^T + b_l) and z_L = h_{L-1} W_L^T WITHOUT its bias, as the head kernels
+    take it (f64 MFMA GEMM, csrc/gemm.hip, in the tiling ops.gemm_nt_variant gives).  hs_out
+    (L - 1 tensors) / z_out: optional buffers for the results (the graph loop's static ones)."""
+    n, L = x.shape[0], len(Ws)
+    hs = [ops.layer_forward(x, Ws[0], bs[0], out=_at(hs_out, 0))]
+    for l in range(1, L - 1):
+        hs.append(ops.gemm_nt(hs[-1], Ws[l], bias=bs[l], relu=True, out=_at(hs_out, l),
+                              variant=ops.gemm_nt_variant(n, Ws[l].shape[0])))
+    zL = ops.gemm_nt(hs[-1], Ws[L - 1], out=z_out,
+                     variant=ops.gemm_nt_variant(n, Ws[L - 1].shape[0]))
+    return hs, zL
+
+
+def hidden_backward(dz, x, Ws, hs, dW_out=None, db_out=None, dz_out=None, ws_wgrad=None,
+                    ws_hidden=None, ws_layer=None, layer_db_out=None):
+    """([dW_1 .. dW_L], [db_1 .. db_{L-1}]) from dz = dL/dz_L, on one stream.  0-based below:
+    Ws[l] = W_{l+1} (Ws[0] is not read), hs[l] = h_{l+1}.  For l = L-1 .. 1 the split-K
+    dW = dz^T h_{l-1} (csrc/wgrad.hip), then (dz, db) of the layer below (ops.hidden_backward,
+    csrc/gemm.hip); then layer 1's dW from dz_1 (its ReLU mask is idempotent on the masked dz_1).
+    Optional, indexed by l: dW_out, db_out and dz_out (the layer's own), ws_wgrad and ws_hidden
+    (entry 0 unused); ws_layer and layer_db_out are layer 1's scratch and its repeated db_1."""
+    L = len(hs) + 1
+    dW, db = [None] * L, [None] * (L - 1)
+    for l in range(L - 1, 0, -1):
+        dW[l] = ops.weight_grad(dz, hs[l - 1], out=_at(dW_out, l), ws=_at(ws_wgrad, l))
+        dz, db[l - 1] = ops.hidden_backward(dz, Ws[l], hs[l - 1], ws=_at(ws_hidden, l),
+                                            dz_out_buf=_at(dz_out, l - 1),
+                                            db_out=_at(db_out, l - 1))
+    dW[0], _ = ops.layer_backward(dz, hs[0], x, ws=ws_layer, dW_out=_at(dW_out, 0),
+                                  db_out=layer_db_out)
+    return dW, db

@@ -24,6 +24,9 @@ import os
 import torch
 import torch.nn as nn
 
+from . import kernel_path
+from .kernel_path import MULTILAYER_MAX, MULTILAYER_MIN, linear_layers  # noqa: F401
+
 LOG_STD_EPS = 1e-7  # src/utils/dtypes.py:7, used inside get_log_p (policy.py:49)
 LOG_2PI = math.log(2 * math.pi)
 SPLITK_MIN_ROWS = 16384
@@ -151,28 +154,20 @@ class _TwoLayerLogp(torch.autograd.Function):
         return None, dW1, db1, dW2, db2, dWm, dbm, dls, None
 
 
-MULTILAYER_MIN, MULTILAYER_MAX = 3, 6  # hidden layers of _MultiLayerLogp (2 L + 3 <= 16 tensors)
-
-
 def multilayer_ok(widths, num_features):
     """True for the hidden widths _MultiLayerLogp takes: 3 to 6 layers, all even (16-B aligned
     weight rows for the matrix-core kernels), behind an input layer of at most 64 features."""
-    return (MULTILAYER_MIN <= len(widths) <= MULTILAYER_MAX and num_features <= 64
-            and all(w % 2 == 0 for w in widths))
+    return kernel_path.network_kind(widths, num_features) == kernel_path.MULTILAYER
 
 
 class _MultiLayerLogp(torch.autograd.Function):
     """log p(a | s) of a ReLU policy with L >= 3 hidden layers for a large batch, from the
     library's kernels only (args: x, actions, W_1, b_1, ..., W_L, b_L, Wm, bm, log_std):
 
-    layer 1        h_1 = relu(x W_1^T + b_1)             csrc/mlp.hip
-    layers 2..L-1  h_l = relu(h_{l-1} W_l^T + b_l)       f64 MFMA GEMM (csrc/gemm.hip)
-    layer L        z_L = h_{L-1} W_L^T                    the same GEMM without bias / ReLU
+    layers 1..L    h_1 .. h_{L-1} and z_L                 kernel_path.hidden_forward
     head           logp(relu(z_L + b_L) Wm^T + bm)        csrc/head.hip, b_L + ReLU folded in
-    backward: head (dz_L, dWm, dbm, dlog_std, db_L), then for l = L .. 2 the split-K
-    dW_l = dz_l^T h_{l-1} (csrc/wgrad.hip) and (dz_{l-1}, db_{l-1}) = hidden_backward(dz_l, W_l,
-    h_{l-1}) (csrc/gemm.hip), then layer 1's dW_1 from dz_1 (its ReLU mask is idempotent on the
-    already masked dz_1).  Same math as nn.Linear/ReLU."""
+    backward: head (dz_L, dWm, dbm, dlog_std, db_L), then kernel_path.hidden_backward down to
+    layer 1.  Same math as nn.Linear/ReLU."""
 
     @staticmethod
     def forward(ctx, x, actions, *params):
@@ -181,12 +176,7 @@ class _MultiLayerLogp(torch.autograd.Function):
         L = (len(params) - 3) // 2
         Ws, bs = params[0:2 * L:2], params[1:2 * L:2]
         Wm, bm, log_std = params[2 * L:]
-        n = x.shape[0]
-        hs = [ops.layer_forward(x, Ws[0], bs[0])]
-        for l in range(1, L - 1):
-            hs.append(ops.gemm_nt(hs[-1], Ws[l], bias=bs[l], relu=True,
-                                  variant=ops.gemm_nt_variant(n, Ws[l].shape[0])))
-        zL = ops.gemm_nt(hs[-1], Ws[L - 1], variant=ops.gemm_nt_variant(n, Ws[L - 1].shape[0]))
+        hs, zL = kernel_path.hidden_forward(x, Ws, bs)
         mu, logp = ops.head_forward(zL, Wm, bm, log_std, actions, bz=bs[L - 1])
         ctx.L = L
         ctx.save_for_backward(x, actions, zL, mu, Wm, log_std, bs[L - 1], *Ws[1:], *hs)
@@ -202,13 +192,8 @@ class _MultiLayerLogp(torch.autograd.Function):
         hs = ctx.saved_tensors[7 + L - 1:]              # hs[l] = h_{l+1}
         dz, dWm, dbm, dls, dbL = ops.head_backward(g.contiguous(), zL, Wm, log_std, actions, mu,
                                                    bz=bL, need_dz=True)
-        dW, db = [None] * L, [None] * L
-        db[L - 1] = dbL
-        for l in range(L - 1, 0, -1):
-            dW[l] = ops.weight_grad(dz, hs[l - 1])
-            dz, db[l - 1] = ops.hidden_backward(dz, Ws[l], hs[l - 1])
-        dW[0], _ = ops.layer_backward(dz, hs[0], x)
-        grads = [t for pair in zip(dW, db) for t in pair]
+        dW, db = kernel_path.hidden_backward(dz, x, Ws, hs)
+        grads = [t for pair in zip(dW, db + [dbL]) for t in pair]
         return (None, None, *grads, dWm, dbm, dls)
 
 
@@ -237,9 +222,8 @@ class GaussianPolicy(nn.Module):
 
     def initialize_weights(self):
         nn.init.xavier_uniform_(self.mean.weight)
-        for layer in self.net:
-            if isinstance(layer, nn.Linear):
-                nn.init.xavier_uniform_(layer.weight)
+        for layer in linear_layers(self):
+            nn.init.xavier_uniform_(layer.weight)
 
     @property
     def device(self):
@@ -255,20 +239,23 @@ class GaussianPolicy(nn.Module):
         """min_rows: the caller's own floor (the sharded iteration's), default fused_min_rows()."""
         floor = fused_min_rows() if min_rows is None else min_rows
         return (states.is_cuda and states.dim() == 2 and states.shape[0] >= floor
-                and self.activation is nn.ReLU and self.action_dim <= 32
-                and self.mean.in_features <= 512 and states.dtype == torch.float64
+                and self.activation is nn.ReLU
+                and self.action_dim <= kernel_path.HEAD_MAX_ACTIONS
+                and self.mean.in_features <= kernel_path.HEAD_MAX_WIDTH
+                and states.dtype == torch.float64
                 and actions.dtype == torch.float64)
 
     def get_log_p(self, states, actions):
         """sum_a -0.5 (log 2pi + 2 log_std + (a - mu)^2 / (exp(log_std) + 1e-7)^2)."""
         if self._fused_head_ok(states, actions):
-            layers = [m for m in self.net if isinstance(m, nn.Linear)]
-            if len(layers) == 2 and self.num_features <= 64:
+            layers = linear_layers(self)
+            kind = kernel_path.network_kind([m.out_features for m in layers], self.num_features)
+            if kind == kernel_path.TWO_LAYER:
                 l1, l2 = layers
                 return _TwoLayerLogp.apply(states.contiguous(), l1.weight.contiguous(), l1.bias,
                                            l2.weight, l2.bias, self.mean.weight.contiguous(),
                                            self.mean.bias, self.log_std, actions.contiguous())
-            if multilayer_ok([m.out_features for m in layers], self.num_features):
+            if kind == kernel_path.MULTILAYER:
                 flat = [t for m in layers for t in (m.weight.contiguous(), m.bias)]
                 return _MultiLayerLogp.apply(states.contiguous(), actions.contiguous(), *flat,
                                              self.mean.weight.contiguous(), self.mean.bias,

@@ -39,8 +39,9 @@ DEEP4 = (HEAD + 3 * [("weight_grad", "fork"), ("hidden_backward", "main")]
 
 
 class _Recorder:
-    """Stands in for the name `ops` of the device_loop module: calls made through it are noted
-    with the stream they were issued on; calls ops functions make to each other are not."""
+    """Stands in for the name `ops` of the device_loop and kernel_path modules: calls made
+    through it are noted with the stream they were issued on; calls ops functions make to each
+    other are not."""
 
     def __init__(self, ops, it, calls):
         self._ops, self._it, self._calls = ops, it, calls
@@ -66,7 +67,7 @@ class _Recorder:
     ([64, 48, 32, 16], "1", "MultiLayerIteration", DEEP4),
 ], ids=["two-layer-fused", "two-layer-unfused", "deep4"])
 def test_body_launch_list(cuda, monkeypatch, hid, fused, cls, expected):
-    from mepol_amd import ops
+    from mepol_amd import kernel_path, ops
     from mepol_amd.algorithms import device_loop
 
     monkeypatch.delenv("MEPOL_FUSED_MIN_ROWS", raising=False)
@@ -90,7 +91,9 @@ def test_body_launch_list(cuda, monkeypatch, hid, fused, cls, expected):
     theta = [p.detach().clone() for p in tgt.parameters()]
 
     calls = []
-    monkeypatch.setattr(device_loop, "ops", _Recorder(ops, it, calls))
+    recorder = _Recorder(ops, it, calls)
+    monkeypatch.setattr(device_loop, "ops", recorder)
+    monkeypatch.setattr(kernel_path, "ops", recorder)  # the deep forward's chain is made there
     it._warmup()  # one eager body on the side stream, enable flag 0
     torch.cuda.synchronize()
 

@@ -44,20 +44,53 @@ def iw_normalize(u, U):
     return u / U
 
 
-def entropy_forward(w, idxT, D, k, ns, G, B, eps, n_w=None):
+def entropy_forward(w, idxT, D, k, ns, G, B, eps, n_w=None, g_out=None, out4=None, vals=None):
+    """ops.entropy_forward, its emit form included: with `vals` (and `out4`) given, vals =
+    {out4[0] on entry, new KL} and out4 is then overwritten in place."""
     w = w.numpy()
     I = idxT.numpy().T
     Dn = D.numpy()
     n_w = w.shape[0] if n_w is None else n_w
     W = w[I[:, :k]].sum(1)
-    V = (Dn[:, k] ** ns * np.pi ** (ns / 2)) / G
-    r = W / (V + eps)
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        V = (Dn[:, k] ** ns * np.pi ** (ns / 2)) / G
+        r = W / (V + eps)
         term = (W / k) * np.log(r + eps)
         klt = np.log(k / (n_w * W) + eps)
         g = -(1.0 / k) * (np.log(r + eps) + r / (r + eps))
-    out4 = np.array([-term.sum() + B, klt.sum() / n_w, term.sum(), klt.sum()])
-    return torch.as_tensor(out4), torch.as_tensor(W), torch.as_tensor(g)
+        new4 = np.array([-term.sum() + B, klt.sum() / n_w, term.sum(), klt.sum()])
+    g = torch.as_tensor(g)
+    if g_out is not None:
+        g = g_out.copy_(g)
+    if vals is not None:
+        assert out4 is not None
+        vals[0] = out4[0]
+        vals[1] = float(new4[1])
+    new4 = torch.as_tensor(new4)
+    out4 = out4.copy_(new4) if out4 is not None else new4
+    return out4, torch.as_tensor(W), g
+
+
+def iw_normalize_gathered(xu_all, world, n, nt, w_out):
+    """ops.iw_normalize_gathered: w_out [world n] from the [u | trajectory sums] blocks."""
+    x = xu_all.numpy().reshape(world, n + nt)
+    U = x[:, n:].sum()
+    w_out.copy_(torch.as_tensor((x[:, :n] / U).reshape(-1)))
+    return w_out
+
+
+def sharded_emit(x_all, world, stride, off, B, n_global, sums_cur, vals):
+    """ops.sharded_emit: vals <- (B - sums_cur[0], rank-order sum of x[r, off + 1] / n_global),
+    sums_cur <- the rank-order sums of x[r, off], x[r, off + 1]."""
+    x = x_all.numpy().reshape(world, stride)
+    s0, s1 = 0.0, 0.0
+    for r in range(world):
+        s0 += float(x[r, off])
+        s1 += float(x[r, off + 1])
+    vals[0] = B - float(sums_cur[0])
+    vals[1] = s1 / n_global
+    sums_cur[0] = s0
+    sums_cur[1] = s1
 
 
 def csr_build(idxT, k, n_own, col_offset=0, row_offset=0, nq=None):

@@ -397,7 +397,8 @@ int mepol_rollout_step(int env_id, double* env_f64, float* env_f32, const double
  * constructed at mepol.py:308-311, over n_tensors (<= 16) f64 parameter tensors, one launch per 8 of them.
  * exp_avg (Adam only) / exp_avg_sq (Adam; RMSprop square_avg) are updated in place.
  * scalars is DEVICE memory: Adam {enable, lr/bias_correction1, sqrt(bias_correction2), beta1,
- * beta2, eps}; RMSprop {enable, lr, alpha, eps}.  enable == 0 makes the call a no-op. */
+ * beta2, eps}; RMSprop {enable, lr, alpha, eps}.  enable == 0 makes the call a no-op.  A tensor
+ * of size 0 is skipped; its pointers may be NULL. */
 int mepol_optim_step(int kind, int n_tensors, double* const* params, const double* const* grads,
                      double* const* exp_avg, double* const* exp_avg_sq, const int64_t* sizes,
                      const double* scalars, void* stream);

@@ -105,6 +105,7 @@ extern "C" int mepol_optim_step_snapshot(int kind, int n_tensors, double* const*
     return kErrBadArg;
   }
   for (int i = 0; i < n_tensors; ++i) {
+    if (sizes[i] == 0) continue;  // an empty tensor has no storage: its pointers may be null
     if (!params[i] || !grads[i] || !exp_avg_sq[i] || (kind == 0 && !exp_avg[i]) || sizes[i] < 0) {
       set_error("mepol_optim_step: null tensor %d", i);
       return kErrBadArg;

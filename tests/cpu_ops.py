@@ -125,3 +125,94 @@ def entropy_reverse_scan(gamma, w, partials, nparts, offsets, nt, T_stride, grad
         seg = c[off[n]:off[n + 1]]
         out[n, :len(seg)] = np.cumsum(seg[::-1])[::-1]
     return torch.as_tensor(out * float(grad_H))
+
+
+# ---------------------------------------------------------------------------------------------
+# The Gaussian head, the input layer and the optimizer (csrc/head.hip, mlp.hip, optim.hip) in
+# plain f64 numpy, from the formulas in those files' header comments.
+# ---------------------------------------------------------------------------------------------
+_LOG2PI = float(np.log(2.0 * np.pi))
+_STD_EPS = 1e-7
+
+
+def _np(t):
+    return None if t is None else t.numpy()
+
+
+def _into(out, value):
+    value = torch.as_tensor(np.ascontiguousarray(value))
+    return value if out is None else out.copy_(value.reshape(out.shape))
+
+
+def _relu_in(z, bz):
+    pre = _np(z) + _np(bz) if bz is not None else _np(z)
+    return pre, np.maximum(pre, 0.0)
+
+
+def head_forward(z, Wm, bm, log_std, act, bz=None, mu_out=None, logp_out=None):
+    _, x = _relu_in(z, bz)
+    mu = x @ _np(Wm).T + _np(bm)
+    ls = _np(log_std)
+    sigma = np.exp(ls) + _STD_EPS
+    d = _np(act) - mu
+    logp = (-0.5 * (_LOG2PI + 2.0 * ls + d * d / (sigma * sigma))).sum(axis=1)
+    return _into(mu_out, mu), _into(logp_out, logp)
+
+
+def head_backward(grad_logp, z, Wm, log_std, act, mu, bz=None, need_dz=True, ws=None,
+                  outs=None, reduce_stream=None, defer_reduce=False):
+    pre, x = _relu_in(z, bz)
+    W, ls, g = _np(Wm), _np(log_std), _np(grad_logp).reshape(-1, 1)
+    e = np.exp(ls)
+    sigma = e + _STD_EPS
+    d = _np(act) - _np(mu)
+    dmu = g * d / (sigma * sigma)
+    dls = (g * (-1.0 + d * d * (e / (sigma * sigma * sigma)))).sum(axis=0)
+    dz = np.where(pre > 0.0, dmu @ W, 0.0)
+    o = outs if outs is not None else (None, None, None, None)
+    res = (torch.as_tensor(dz) if need_dz else None, _into(o[0], dmu.T @ x),
+           _into(o[1], dmu.sum(axis=0)), _into(o[2], dls),
+           _into(o[3], dz.sum(axis=0)) if bz is not None else None)
+    return res + ((lambda: None),) if defer_reduce else res
+
+
+def layer_forward(x, W, b, out=None):
+    return _into(out, np.maximum(_np(x) @ _np(W).T + _np(b), 0.0))
+
+
+def layer_backward(dh, h, x, ws=None, dW_out=None, db_out=None):
+    dz = np.where(_np(h) > 0.0, _np(dh), 0.0)
+    return _into(dW_out, dz.T @ _np(x)), _into(db_out, dz.sum(axis=0))
+
+
+def layer_tangent(x, dW, db, h, out=None):
+    return _into(out, np.where(_np(h) > 0.0, _np(x) @ _np(dW).T + _np(db), 0.0))
+
+
+def optim_step(kind, params, grads, exp_avg, exp_avg_sq, scalars, snapshot=None):
+    """csrc/optim.hip's op sequence, one f64 rounding per op, in place; scalars[0] == 0: nothing
+    is written.  Snapshots (lists or None) receive the values from before the update."""
+    sc = [float(s) for s in _np(scalars)]
+    if sc[0] == 0.0:
+        return
+    ps, ms, vs = snapshot if snapshot is not None else (None, None, None)
+    with np.errstate(all="ignore"):
+        for i, (p, g, v) in enumerate(zip(params, grads, exp_avg_sq)):
+            p, g, v = p.numpy(), g.numpy(), v.numpy()
+            if ps is not None:
+                ps[i].copy_(torch.as_tensor(p.copy()))
+            if vs is not None:
+                vs[i].copy_(torch.as_tensor(v.copy()))
+            if kind == 0:
+                step_size, bc2_sqrt, b1, b2, eps = sc[1:6]
+                m = exp_avg[i].numpy()
+                if ms is not None:
+                    ms[i].copy_(torch.as_tensor(m.copy()))
+                w1, w2 = 1.0 - b1, 1.0 - b2
+                m[...] = m + w1 * (g - m)
+                v[...] = v * b2 + w2 * (g * g)
+                p[...] = p + (-step_size) * (m / (np.sqrt(v) / bc2_sqrt + eps))
+            else:
+                lr, alpha, eps = sc[1:4]
+                v[...] = v * alpha + (1.0 - alpha) * (g * g)
+                p[...] = p + (-lr) * (g / (np.sqrt(v) + eps))

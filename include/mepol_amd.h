@@ -209,6 +209,68 @@ int mepol_rollout_deep(int env_id, int n_hidden, const int* widths, const double
 int mepol_rollout_deep_workspace_size(int64_t n, int64_t T, int n_hidden, const int* widths,
                                       int a_dim, size_t* bytes);
 
+/* ---- TRPO sampling and batch processing (src/algorithms/trpo.py:86-201, 308-331) -------------
+ * Every entry point below takes device pointers, only enqueues, returns 0 without a launch for
+ * n <= 0, and validates every other argument on the host before any launch.
+ *
+ * mepol_rollout_mlp with early termination and sparse rewards: collect_sample_batch's episodes
+ * (trpo.py:118-140) for CustomRewardEnv(GridWorldContinuous(), grid_goal*) (goal_rl.py:61-77).
+ * env_id 1 = GridWorld; env_id 0 returns MEPOL_ERR_UNSUPPORTED.  After each env step the f32 state
+ * (sx, sy) is tested against the goal in f32, every operation rounded on its own:
+ *     dx = sx - goal_x, dy = sy - goal_y, nrm = sqrt(fl(fl(dx dx) + fl(dy dy))),
+ *     hit <=> (double)nrm <= radius          (np.linalg.norm(s - goal) <= 1e-1 under numpy 1.x).
+ * A hit at step t (0-based) gives rewards_rec[i, t] = 1, len_out[i] = t + 1, done_out[i] = 1,
+ * s_{t+1} is recorded and the trajectory's workgroup(s) leave; with no hit len_out[i] = T and
+ * done_out[i] = 0.  Every output is fully defined by the call: states_rec [n,T+1,2] rows past len,
+ * actions_rec [n,T,2] and rewards_rec [n,T] rows from len on are written as zeros.  Policy, noise,
+ * forms, summation order and workspace (error word, mail) as for mepol_rollout_mlp: up to the end
+ * of each episode the recorded states and actions are the bits mepol_rollout_mlp records. */
+int mepol_rollout_goal(int env_id, const double* W1, const double* b1, int h0, const double* W2t,
+                       const double* b2, int h1, const double* Wm, const double* bm,
+                       const double* log_std, int a_dim, const float* init32, const double* noise,
+                       int64_t n, int64_t T, float goal_x, float goal_y, double radius,
+                       float* states_rec, float* actions_rec, float* rewards_rec,
+                       int32_t* len_out, int32_t* done_out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int mepol_rollout_goal_workspace_size(int env_id, int64_t n, int64_t T, int h0, int h1, int a_dim,
+                                      size_t* bytes);
+/* mepol_rollout_mlp_plan_info for mepol_rollout_goal (a_dim = 2): its form is chosen by the
+ * goal-mode kernel's own occupancy; k_chunks is the same. */
+int mepol_rollout_goal_plan_info(int64_t n, int h0, int h1, int a_dim, int* workgroups_per_traj,
+                                 int* k_chunks);
+/* The step budget of collect_sample_batch (`steps == batch_size`, trpo.py:98-140) over a batch
+ * that was rolled out in parallel: trajectories are taken in index order while the running sum of
+ * len [n] is below `budget`, and the last one is cut so that the sum equals it.  len_out [n] = the
+ * kept lengths (0 for unused trajectories), done_out [n] = done && len_out == len (a cut
+ * trajectory is not done), offsets [n+1] int64 = exclusive prefix sum of len_out, meta [2] int64 =
+ * {trajectories used, steps kept (< budget when the batch is too short)}.  One workgroup;
+ * n > 65536 returns MEPOL_ERR_UNSUPPORTED. */
+int mepol_traj_budget(const int32_t* len, const int32_t* done, int64_t n, int64_t budget,
+                      int32_t* len_out, int32_t* done_out, int64_t* offsets, int64_t* meta,
+                      void* stream);
+/* process_traj (trpo.py:175-201) over n ragged trajectories and the concatenation of :308-326.
+ * rewards [n,T] f32, values [n,T+1] f64 (the critic at every recorded state), len / done / offsets
+ * as mepol_traj_budget writes them, states_rec [n,T+1,num_features] f32, actions_rec [n,T,a_dim]
+ * f32.  Packed outputs over n_out = offsets[n] rows, row offsets[i] + t <-> step t < len[i] of
+ * trajectory i: targets, adv [n_out] f64, states_out [n_out,num_features] and actions_out
+ * [n_out,a_dim] f64 (exact widenings).  All in f64, each operation rounded on its own:
+ *     boot = done[i] ? 0 : values[i][len[i]]
+ *     c = boot;  t = len-1 .. 0:  c = r_t + gamma c;                       targets = c
+ *     A = 0;     t = len-1 .. 0:  A = ((r_t + gamma vn) - values[i][t]) + (gamma lambd) A,
+ *                                 vn = t == len-1 ? boot : values[i][t+1];  adv = A
+ * Rows whose len / offsets do not fit [0, T] / n_out are skipped (nothing is written for them). */
+int mepol_gae(const float* rewards, const double* values, const int32_t* len, const int32_t* done,
+              const int64_t* offsets, int64_t n, int64_t T, int64_t n_out, double gamma,
+              double lambd, const float* states_rec, int num_features, const float* actions_rec,
+              int a_dim, double* targets, double* adv, double* states_out, double* actions_out,
+              void* stream);
+/* out = (x - mean) / sqrt(mean((x - mean)^2)) over x [n] f64 (trpo.py:331, numpy's population
+ * std), the two sums through fixed-order block partials: the same bits on every call.  A zero std
+ * gives non-finite values, as numpy does.  out may alias x. */
+int mepol_standardize_workspace_size(int64_t n, size_t* bytes);
+int mepol_standardize(const double* x, int64_t n, double* out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* ---- policy MLP (GaussianPolicy, src/policy.py:16-51) for the large-batch passes -----------
  * Gaussian head: mean layer + log-probability with the last hidden layer's bias and ReLU folded
  * in.  z [n, hidden] is the last hidden layer's PRE-activation WITHOUT its bias bz (nullable);

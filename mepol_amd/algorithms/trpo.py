@@ -1,8 +1,16 @@
-"""TRPO's natural-gradient policy step for GaussianPolicy (src/algorithms/trpo.py:14-84, 345-424).
+"""TRPO for GaussianPolicy: drop-in for src/algorithms/trpo.py of the reference.
 
-The reference takes every Hessian-vector product of KL(theta_0 || theta) by a double backward
-through policy(states).  All cg_iters + 1 products of a step are taken at the same theta_0 over
-the same states, and at theta_0 the Hessian has a closed form ("TRPO policy step"):
+  collect_sample_batch(env, policy, batch_size, traj_len, num_workers)           :86-172
+  process_traj(gamma, lambd, vfuncs, states, actions, rewards, boot_value)       :175-201
+  trpo(env_maker, env_name, num_epochs, batch_size, traj_len, ...)               :204-493
+  conj_gradient, assign_flat_params, backtracking                                :14-84
+  trpo_step: the policy update inside trpo()                                     :345-424
+  process_batch: the per-trajectory loop and concatenation inside trpo()         :281-331
+
+Policy step.  The reference takes every Hessian-vector product of KL(theta_0 || theta) by a double
+backward through policy(states).  All cg_iters + 1 products of a step are taken at the same
+theta_0 over the same states, and at theta_0 the Hessian has a closed form ("TRPO
+policy step"):
 
     network parameters   H v = (1/n) sum_i J_i^T diag(1 / (u + 1e-7)) J_i v,  u = exp(2 log_std),
                          J_i = d mu_i / d theta_net
@@ -16,20 +24,31 @@ FVP_MIN_ROWS, CPU tensors) use the reference's own method, a double backward ove
 F.linear restatement of mu (it must not go through policy._Linear, whose weight gradient is a
 kernel call without an autograd graph behind it).
 
+Sampling and batch processing ("TRPO sampling and batch processing").  The reference
+steps one env at a time through policy.predict.  For a GridWorld goal env and the two-layer policy
+(kernel_path.goal_sampler) collect_sample_batch rolls whole rounds of trajectories out in one
+launch each (ops.rollout_goal: termination and the sparse reward inside the kernel), applies the
+reference's step budget on the device (ops.traj_budget) and reads two words per round;
+process_batch computes targets, GAE advantages and the packed batch with ops.gae and
+ops.standardize.  Every other env, policy or device takes the reference's sequential loop, and
+CPU tensors a numpy restatement of the same arithmetic.  The critic stays a torch module under
+autograd.
+
 conj_gradient, assign_flat_params and backtracking keep the reference's names, argument order
-and control flow; trpo_step is its policy update (old log-probabilities, gain and gradient,
-conjugate gradient, Lagrange multiplier, backtracking line search).  Sampling, the critic and
-the goal_rl command line are not part of this module.
+and control flow.
 """
 import math
 import os
+import time
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import kernel_path, ops
 from .. import policy as _policy
+from ..envs.wrappers import unwrap
 from ..kernel_path import linear_layers
 
 KL_VAR_EPS = 1e-7  # the epsilon on the variance in the reference's KL (trpo.py:384)
@@ -333,3 +352,320 @@ def trpo_step(policy, states, actions, advantages, kl_thresh, cg_iters=10, cg_da
     success, _, backtrack_iters = backtracking(policy, objective, compute_kl, kl_thresh, x,
                                                1 / lagrange, max_iters=max_backtracks)
     return success, backtrack_iters
+
+
+# ---------------------------------------------------------------------------------------------
+# Sampling (trpo.py:86-172)
+# ---------------------------------------------------------------------------------------------
+# What the last collect_sample_batch call did: "path" is "kernel" or "host", "rounds" the kernel
+# path's rollout launches; "kernel_batches" / "host_batches" count calls since import.
+SAMPLER_STATS = {"path": None, "rounds": 0, "kernel_batches": 0, "host_batches": 0}
+
+ROUND_MAX_TRAJ = 65536  # mepol_traj_budget's limit
+_ROUND_CAPACITY = {}
+
+
+def _round_capacity(h0, h1, a_dim, device):
+    """Trajectories per round that cost no more time than one: the most for which
+    ops.rollout_goal_plan (the goal kernel's own occupancy) still reports the multi-workgroup
+    form, found once per shape and MEPOL_ROLLOUT_MW setting by bisection, or, where there is no
+    such form, one workgroup per CU."""
+    key = (h0, h1, a_dim, device, os.environ.get("MEPOL_ROLLOUT_MW"))
+    if key not in _ROUND_CAPACITY:
+        def multi(n):
+            return ops.rollout_goal_plan(n, h0, h1, a_dim)["workgroups_per_traj"] > 1
+
+        lo, hi = 0, 1 << 16  # multi(n) holds up to some n < hi (no device holds 65,536 parts)
+        while lo + 1 < hi:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if multi(mid) else (lo, mid)
+        _ROUND_CAPACITY[key] = lo or torch.cuda.get_device_properties(device).multi_processor_count
+    return _ROUND_CAPACITY[key]
+
+
+def _draw_round(base, R, T, a_dim, device, generator):
+    """Initial states f32 [R, 2] and action noise f64 [T, R, a] of one round, in this order."""
+    init = base.reset_batch_torch(R, device, generator)
+    noise = torch.randn((T, R, a_dim), dtype=torch.float64, device=device, generator=generator)
+    return init, noise
+
+
+def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, round_traj):
+    dev = policy.device
+    base = unwrap(env)
+    a_dim = policy.action_dim
+    (W1, b1), (W2, b2) = layers
+    head = (policy.mean.weight.detach(), policy.mean.bias.detach(), policy.log_std.detach())
+    cap = _round_capacity(W1.shape[0], W2.shape[0], a_dim, dev)
+    steps_idx = torch.arange(T + 1, device=dev)
+    remaining, rounds, parts = int(batch_size), 0, []
+    while remaining > 0:
+        R = int(round_traj) if round_traj else max(-(-remaining // T), cap)
+        R = min(R, ROUND_MAX_TRAJ)
+        init, noise = (draw(R, T, a_dim, dev) if draw is not None
+                       else _draw_round(base, R, T, a_dim, dev, generator))
+        states = torch.empty((R, T + 1, 2), dtype=torch.float32, device=dev)
+        actions = torch.empty((R, T, a_dim), dtype=torch.float32, device=dev)
+        rewards = torch.empty((R, T), dtype=torch.float32, device=dev)
+        lens = torch.empty(R, dtype=torch.int32, device=dev)
+        dones = torch.empty(R, dtype=torch.int32, device=dev)
+        roll = (W1, b1, W2, b2, *head, init.to(torch.float32), noise, goal.goal, goal.radius,
+                states, actions, rewards, lens, dones)
+        err, rerun = ops.rollout_goal(*roll, defer_check=True)
+        kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
+        # the round's one host synchronisation: {trajectories used, steps kept, error word}
+        m, kept, bad = torch.cat([meta, err.to(torch.int64)]).tolist()
+        if bad:
+            rerun()
+            kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
+            m, kept = meta.tolist()
+        rounds += 1
+        # a budget-cut last trajectory keeps the state it reached and nothing behind it, as the
+        # reference's arrays do; that takes the reward of a goal it reached behind the cut, too
+        last = kept_len[m - 1]
+        states[m - 1].masked_fill_((steps_idx > last)[:, None], 0)
+        actions[m - 1].masked_fill_((steps_idx[:T] >= last)[:, None], 0)
+        rewards[m - 1].masked_fill_(steps_idx[:T] >= last, 0)
+        parts.append((states[:m], actions[:m], rewards[:m], kept_len[:m], kept_done[:m]))
+        remaining -= kept
+    SAMPLER_STATS.update(path="kernel", rounds=rounds)
+    SAMPLER_STATS["kernel_batches"] += 1
+    st, ac, rw, ln, dn = (torch.cat(x) if len(parts) > 1 else x[0] for x in zip(*parts))
+    return st, ac, rw, ln.reshape(-1, 1), dn.reshape(-1, 1).bool()
+
+
+def _collect_host(env, policy, batch_size, traj_len):
+    """The reference's one-worker loop (trpo.py:87-157): one env, one policy.predict per step."""
+    steps = 0
+    nf = env.num_features
+    a_dim = env.action_space.shape[0]
+    total = []
+    while steps < batch_size:
+        states = np.zeros((1, traj_len + 1, nf), dtype=np.float32)
+        actions = np.zeros((1, traj_len, a_dim), dtype=np.float32)
+        rewards = np.zeros((1, traj_len), dtype=np.float32)
+        s = env.reset()
+        done, t = False, -1
+        for t in range(traj_len):
+            states[0, t] = s
+            a = policy.predict(s).numpy()
+            actions[0, t] = a
+            ns, r, done, _ = env.step(a)
+            rewards[0, t] = r
+            s = ns
+            steps += 1
+            if done is True or steps == batch_size:
+                break
+        states[0, t + 1] = s
+        total.append((states, actions, rewards, np.array([[t + 1]], dtype=np.int32),
+                      np.array([[done]], dtype=bool)))
+    SAMPLER_STATS.update(path="host", rounds=0)
+    SAMPLER_STATS["host_batches"] += 1
+    dev = getattr(policy, "device", torch.device("cpu"))
+    return tuple(torch.as_tensor(np.vstack(x), device=dev) for x in zip(*total))
+
+
+def collect_sample_batch(env, policy, batch_size, traj_len, num_workers=1, generator=None,
+                         draw=None, round_traj=None):
+    """Trajectories of at most traj_len steps until exactly batch_size steps are collected, the
+    last one cut (trpo.py:86-172).  Returns tensors on the policy's device: states f32
+    [m, T+1, nf], actions f32 [m, T, a], rewards f32 [m, T], real_traj_lens int32 [m, 1], dones
+    bool [m, 1]; rows behind a trajectory's end are zero.
+
+    Where kernel_path.goal_sampler takes (env, policy), rounds of R trajectories are rolled out
+    in one launch each and cut to the remaining budget on the device; taking the first m of a
+    parallel round in index order has the distribution of the reference's sequential sampling
+    (DESIGN.md).  R = round_traj, or the larger of ceil(remaining / traj_len) and the most
+    trajectories the multi-workgroup rollout holds (_round_capacity).  `generator` seeds the
+    draws; `draw(R, T, a, device) -> (init f32 [R, 2], noise f64 [T, R, a])` replaces them
+    (tests).  num_workers is ignored there.  Everything else runs the reference's sequential
+    loop with one worker."""
+    if not hasattr(env.action_space, "shape") or hasattr(env.action_space, "n"):
+        raise NotImplementedError("collect_sample_batch: continuous action spaces only")
+    spec = kernel_path.goal_sampler(env, policy)
+    if spec is not None and batch_size > 0:
+        with torch.no_grad():
+            return _collect_kernel(env, policy, *spec, batch_size, int(traj_len), generator, draw,
+                                   round_traj)
+    return _collect_host(env, policy, int(batch_size), int(traj_len))
+
+
+# ---------------------------------------------------------------------------------------------
+# Targets and advantages (trpo.py:175-201, 281-331)
+# ---------------------------------------------------------------------------------------------
+def _np64(x):
+    """x (tensor, array or scalar) as an f64 numpy array; f32 values widen exactly."""
+    if torch.is_tensor(x):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=np.float64)
+
+
+def process_traj(gamma, lambd, vfuncs, states, actions, rewards, boot_value):
+    """Discounted targets and GAE advantages of one trajectory (trpo.py:175-201), on the host.
+    The reference's operator order in f64; unlike the reference the results stay f64 (it rounds
+    every step's value to f32)."""
+    n = np.shape(states)[0]
+    v, r = _np64(vfuncs).reshape(-1), _np64(rewards).reshape(-1)
+    boot = _np64(boot_value).reshape(-1)[0]
+    gamma, lambd = np.float64(gamma), np.float64(lambd)
+    targets = np.zeros(n, dtype=np.float64)
+    curr_target = boot
+    for i in reversed(range(n)):
+        targets[i] = r[i] + gamma * curr_target
+        curr_target = targets[i]
+    advantages = np.zeros(n, dtype=np.float64)
+    curr_advantage = np.float64(0)
+    for i in reversed(range(n)):
+        v_next = boot if i == n - 1 else v[i + 1]
+        advantages[i] = (r[i] + gamma * v_next - v[i]) + gamma * lambd * curr_advantage
+        curr_advantage = advantages[i]
+    return targets, advantages
+
+
+def process_batch(states, actions, rewards, real_traj_lens, dones, values, gamma, lambd):
+    """The epoch's update batch from a sampled one (trpo.py:281-341): per trajectory the first
+    real_traj_len steps, targets and GAE advantages bootstrapped from values[i, len] unless done,
+    concatenated, the advantages standardised.  values f64 [m, T+1]: the critic at every recorded
+    state.  Returns f64 (epoch_states [N, nf], epoch_actions [N, a], epoch_targets [N, 1],
+    epoch_advantages [N]) on the inputs' device.  CUDA inputs take ops.gae + ops.standardize, CPU
+    inputs a numpy restatement of the same arithmetic."""
+    m, T = rewards.shape
+    lens = real_traj_lens.reshape(-1)
+    if states.is_cuda:
+        lens = lens.to(torch.int32)
+        offsets = torch.zeros(m + 1, dtype=torch.int64, device=states.device)
+        torch.cumsum(lens, 0, out=offsets[1:])
+        targets, adv, st, ac = ops.gae(rewards, values.detach().to(torch.float64), lens,
+                                       dones.reshape(-1).to(torch.int32), offsets,
+                                       int(offsets[-1]), gamma, lambd, states, actions)
+        return st, ac, targets.unsqueeze(1), ops.standardize(adv)
+    S, A, R = states.numpy(), actions.numpy(), rewards.numpy()
+    V, L, D = values.detach().numpy().astype(np.float64), lens.numpy(), dones.reshape(-1).numpy()
+    out = []
+    for i in range(m):
+        n = int(L[i])
+        boot = np.float64(0) if D[i] else V[i, n]
+        t, a = process_traj(gamma, lambd, V[i, :n], S[i, :n], A[i, :n], R[i, :n], boot)
+        out.append((S[i, :n].astype(np.float64), A[i, :n].astype(np.float64), t, a))
+    st, ac, targets, adv = (np.concatenate(x) for x in zip(*out))
+    adv = (adv - adv.mean()) / adv.std()
+    return (torch.from_numpy(st), torch.from_numpy(ac), torch.from_numpy(targets).unsqueeze(1),
+            torch.from_numpy(adv))
+
+
+# ---------------------------------------------------------------------------------------------
+# Driver (trpo.py:204-493)
+# ---------------------------------------------------------------------------------------------
+def _fit_critic(vfunc, vfunc_optimizer, optimizer, epoch_states, epoch_targets, critic_reg,
+                critic_iters, critic_batch_size):
+    """The reference's critic update (trpo.py:426-457)."""
+    if optimizer == 'lbfgs':
+        def compute_vfunc_loss():
+            vfunc_optimizer.zero_grad()
+            state_values = vfunc(epoch_states)
+            params = torch.cat([torch.reshape(w, (-1,)) for w in vfunc.parameters()], dim=0)
+            l2 = torch.sum(params ** 2, dim=0)
+            loss = torch.mean((state_values - epoch_targets) ** 2) + critic_reg * l2
+            loss.backward()
+            return loss
+        vfunc_optimizer.step(compute_vfunc_loss)
+        return
+    dataset = torch.utils.data.TensorDataset(epoch_states, epoch_targets)
+    dloader = torch.utils.data.DataLoader(dataset, batch_size=critic_batch_size, shuffle=True,
+                                          drop_last=True)
+    for _ in range(critic_iters):
+        vfunc_optimizer.zero_grad()
+        for mb_states, mb_targets in dloader:
+            vfunc_optimizer.zero_grad()
+            loss = torch.mean((vfunc(mb_states) - mb_targets) ** 2)
+            loss.backward()
+            vfunc_optimizer.step()
+
+
+def trpo(env_maker, env_name, num_epochs, batch_size, traj_len, gamma=0.995, lambd=0.98,
+         vfunc=None, policy=None, optimizer='lbfgs', critic_lr=1e-2, critic_reg=1e-3,
+         critic_iters=1, critic_batch_size=64, cg_iters=10, cg_damping=0.1, kl_thresh=0.01,
+         num_workers=1, out_path=None, seed=None):
+    """The reference's TRPO loop (trpo.py:204-493) on the policy's device in f64, with its
+    outputs: <env_name>.csv (Epoch,NumSamples,ExecutionTime,AverageReturn,BacktrackSuccess,
+    BacktrackIters), log_file.txt and policy_weights under out_path.  Per epoch: sample
+    (collect_sample_batch), one batched critic call over the padded states, process_batch,
+    trpo_step, the critic fit.  The critic is moved to the policy's device and f64."""
+    from .mepol import _save_policy, _summary_writer
+
+    env = env_maker()
+    if not hasattr(env.action_space, "shape") or hasattr(env.action_space, "n"):
+        raise NotImplementedError("trpo: continuous action spaces only")
+    if seed is None:
+        seed = np.random.randint(2 ** 16)
+    env.seed(seed)
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+
+    device = policy.device
+    vfunc.to(device=device, dtype=torch.float64)
+    if optimizer == 'adam':
+        vfunc_optimizer = torch.optim.Adam(vfunc.parameters(), lr=critic_lr)
+    elif optimizer == 'lbfgs':
+        vfunc_optimizer = torch.optim.LBFGS(vfunc.parameters(), lr=critic_lr, max_iter=25)
+    else:
+        raise NotImplementedError()
+
+    writer = _summary_writer(out_path)
+    log_file = open(os.path.join(out_path, 'log_file.txt'), 'a', encoding="utf-8")
+    csv_file_1 = open(os.path.join(out_path, f"{env_name}.csv"), 'w')
+    csv_file_1.write(",".join(['Epoch', 'NumSamples', 'ExecutionTime', 'AverageReturn',
+                               'BacktrackSuccess', 'BacktrackIters']))
+    csv_file_1.write("\n")
+    csv_file_1.flush()
+
+    num_samples = 0
+    for epoch in range(num_epochs):
+        t0 = time.time()
+        states, actions, rewards, real_traj_lens, dones = collect_sample_batch(
+            env, policy, batch_size, traj_len, num_workers)
+        num_traj, _, nf = states.shape
+        with torch.no_grad():
+            values = vfunc(states.to(torch.float64).reshape(-1, nf)).reshape(num_traj, -1)
+        epoch_states, epoch_actions, epoch_targets, epoch_advantages = process_batch(
+            states, actions, rewards, real_traj_lens, dones, values, gamma, lambd)
+        # rewards behind a trajectory's end are zero
+        total_reward = float(rewards.sum(dtype=torch.float64))
+
+        success, backtrack_iters = trpo_step(policy, epoch_states, epoch_actions,
+                                             epoch_advantages, kl_thresh, cg_iters=cg_iters,
+                                             cg_damping=cg_damping)
+        _fit_critic(vfunc, vfunc_optimizer, optimizer, epoch_states, epoch_targets, critic_reg,
+                    critic_iters, critic_batch_size)
+
+        num_samples += epoch_states.shape[0]
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+        execution_time = time.time() - t0
+        average_return = total_reward / num_traj
+
+        writer.add_scalar("Num samples", num_samples, global_step=epoch)
+        writer.add_scalar("Execution time (s)", execution_time, global_step=epoch)
+        writer.add_scalar("AverageReturn", average_return, global_step=epoch)
+        writer.add_scalar("BacktrackSuccess", success, global_step=epoch)
+        writer.add_scalar("BacktrackIters", backtrack_iters, global_step=epoch)
+        table = [["Epoch", epoch], ["Num samples", num_samples],
+                 ["Execution time (s)", f"{execution_time:.3f}"],
+                 ["AverageReturn", f"{average_return:.3f}"], ["BacktrackSuccess", success],
+                 ["BacktrackIters", backtrack_iters]]
+        try:
+            from tabulate import tabulate
+
+            fancy_grid = tabulate(table, headers="firstrow", tablefmt="fancy_grid",
+                                  numalign='right')
+        except ImportError:
+            fancy_grid = "\n".join(f"{a}: {b}" for a, b in table)
+        print(fancy_grid)
+        log_file.write(fancy_grid)
+        log_file.flush()
+        csv_file_1.write(f"{epoch},{num_samples},{execution_time},{average_return},{success},"
+                         f"{backtrack_iters}\n")
+        csv_file_1.flush()
+        _save_policy(policy, os.path.join(out_path, 'policy_weights'))
+    log_file.close()
+    csv_file_1.close()

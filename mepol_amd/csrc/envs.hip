@@ -100,7 +100,42 @@ constexpr unsigned long long kMailEmpty = ~0ull;
 constexpr int kRollMaxA = 8;
 constexpr int kRollChunks = 4;
 
-template <int ENV, int U>
+// Goal mode (GOAL = true, GridWorld only): the sparse-reward episodes of goal_rl.py:61-77 under
+// CustomRewardEnv (wrappers.py:40-52).  After each env step the f32 state is tested against the
+// goal; a hit at step t gives rewards[i, t] = 1, len[i] = t + 1, done[i] = 1, s_{t+1} is recorded
+// and the trajectory's workgroup(s) leave.  Every output row past the end is written as zeros, so
+// the caller's buffers need no clearing.  GOAL = false never reads this argument.
+struct GoalArgs {
+  float x, y;      // the goal
+  double radius;
+  float* rewards;  // [n, T]
+  int* len;        // [n]
+  int* done;       // [n]
+};
+
+// np.linalg.norm(s - goal) <= radius with an f32 state and goal and a Python-float radius
+// (numpy 1.x: the f32 norm is widened for the comparison): every operation rounded on its own.
+__device__ __forceinline__ bool goal_hit(float sx, float sy, const GoalArgs& g) {
+  const float dx = __fsub_rn(sx, g.x), dy = __fsub_rn(sy, g.y);
+  const float q = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+  return (double)__fsqrt_rn(q) <= g.radius;
+}
+
+// Zeros behind an episode of `len` < T steps of trajectory i: states rows len + 1 .. T, action
+// and reward rows len .. T - 1, by all nthr threads of one workgroup.
+__device__ __forceinline__ void goal_zero_tail(int64_t i, int64_t len, int64_t T, int a_dim,
+                                               float* __restrict__ states_rec,
+                                               float* __restrict__ actions_rec,
+                                               float* __restrict__ rewards, int tid, int nthr) {
+  float* s = states_rec + (i * (T + 1) + len + 1) * 2;
+  for (int64_t e = tid; e < (T - len) * 2; e += nthr) s[e] = 0.f;
+  float* a = actions_rec + (i * T + len) * a_dim;
+  for (int64_t e = tid; e < (T - len) * a_dim; e += nthr) a[e] = 0.f;
+  float* r = rewards + i * T + len;
+  for (int64_t e = tid; e < T - len; e += nthr) r[e] = 0.f;
+}
+
+template <int ENV, int U, bool GOAL = false>
 __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, int h0,
     const double* __restrict__ W2t, const double* __restrict__ b2, int h1,
@@ -108,9 +143,11 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     const double* __restrict__ log_std, int a_dim, const double* __restrict__ init64,
     const float* __restrict__ init32, const double* __restrict__ noise, int64_t n, int64_t T,
     float* __restrict__ states_rec, float* __restrict__ actions_rec,
-    double* __restrict__ visited, double* __restrict__ final_state, int KL) {
+    double* __restrict__ visited, double* __restrict__ final_state, int KL, GoalArgs goal) {
+  static_assert(!GOAL || ENV == 1, "goal mode is GridWorld's");
   extern __shared__ double sW2[];  // [KL][blockDim.x]: W2^T rows 0 .. KL - 1
   __shared__ double sx[2];
+  __shared__ int sgoal;  // GOAL: the step just taken reached the goal (thread 0 writes it)
   __shared__ double sh1[kRollMaxH];
   __shared__ double spart[kRollMaxH / 64][kRollMaxA];
   const int64_t i = blockIdx.x;
@@ -139,7 +176,9 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     }
     states_rec[(i * (T + 1)) * 2 + 0] = (float)sx[0];
     states_rec[(i * (T + 1)) * 2 + 1] = (float)sx[1];
+    if constexpr (GOAL) sgoal = 0;
   }
+  int64_t steps = T;  // GOAL: the episode's length
   // thread 0: exp(log_std) once, and the next step's noise loaded a step ahead (its global
   // latency would otherwise sit on the serial tail of every step)
   double sd[kRollMaxA], nz[kRollMaxA];
@@ -226,12 +265,30 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
         visited[(i * T + t) * 2 + 0] = sx[0];
         visited[(i * T + t) * 2 + 1] = sx[1];
       }
+      if constexpr (GOAL) {
+        const bool hit = goal_hit(gx, gy, goal);
+        goal.rewards[i * T + t] = hit ? 1.f : 0.f;
+        if (hit) sgoal = 1;
+      }
     }
     __syncthreads();
+    if constexpr (GOAL) {
+      if (sgoal) {  // workgroup-uniform: written before the barrier, never cleared
+        steps = t + 1;
+        break;
+      }
+    }
   }
   if (j == 0 && final_state) {
     final_state[2 * i] = sx[0];
     final_state[2 * i + 1] = sx[1];
+  }
+  if constexpr (GOAL) {
+    if (j == 0) {
+      goal.len[i] = (int)steps;
+      goal.done[i] = sgoal;
+    }
+    goal_zero_tail(i, steps, T, a_dim, states_rec, actions_rec, goal.rewards, j, blockDim.x);
   }
 }
 
@@ -255,7 +312,7 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
 // PROBE (tools/variants/rollout_probe.hip only): thread 0 of each workgroup accumulates
 // s_memtime spans of the step's phases into probe[blockIdx.x][8]; the product has PROBE = false.
 constexpr int kRollMwWaves = kRollChunks;  // one layer-2 chain per wave
-template <int ENV, bool PROBE = false>
+template <int ENV, bool PROBE = false, bool GOAL = false>
 __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, int h0,
     const double* __restrict__ W2t, const double* __restrict__ b2, int h1,
@@ -265,7 +322,8 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     float* __restrict__ states_rec, float* __restrict__ actions_rec,
     double* __restrict__ visited, double* __restrict__ final_state, int np, int nw,
     unsigned long long* __restrict__ mail, int* __restrict__ err, int* __restrict__ ticket,
-    long long* __restrict__ probe) {
+    long long* __restrict__ probe, GoalArgs goal) {
+  static_assert(!GOAL || ENV == 1, "goal mode is GridWorld's");
   extern __shared__ double sW2[];  // [h0][64]: W2^T rows, this part's 64 columns
   __shared__ double sh1[kRollMaxH];
   __shared__ double spart[kRollMwWaves][64];
@@ -288,6 +346,11 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
   // resident (the host's occupancy check) all parts run at once; with fewer slots (another
   // kernel on the CUs) complete trajectories still finish and free theirs: no deadlock without
   // a cooperative launch.
+  // GOAL: every part steps the same env state, so all parts of a trajectory see the hit at the
+  // same step t.  A part leaves only below, after it has published its own mail word of step t
+  // and read every part's word of step t (it needs them for the action that caused the hit), so
+  // no peer ever waits for a word that will not be written; leaving early only frees its slot
+  // sooner for the tickets behind it.
   __shared__ int sticket;
   if (threadIdx.x == 0) sticket = atomicAdd(ticket, 1);
   __syncthreads();
@@ -340,6 +403,8 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     states_rec[(i * (T + 1)) * 2 + 1] = (float)x1;
   }
   if (tid == 0) sbad = 0;
+  int64_t steps = T;  // GOAL: the episode's length
+  bool hit = false;
   __syncthreads();
   if constexpr (PROBE) pr[6] = -(long long)__builtin_amdgcn_s_memrealtime();
   stamp(-1, 0.0);
@@ -487,10 +552,27 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
       }
     }
     stamp(4, x0);
+    if constexpr (GOAL) {
+      hit = goal_hit(gx, gy, goal);  // the same value in every thread of every part
+      if (rec) goal.rewards[i * T + t] = hit ? 1.f : 0.f;
+      if (hit) {
+        steps = t + 1;
+        break;
+      }
+    }
   }
   if (rec && final_state) {
     final_state[2 * i] = x0;
     final_state[2 * i + 1] = x1;
+  }
+  if constexpr (GOAL) {
+    if (rec) {
+      goal.len[i] = (int)steps;
+      goal.done[i] = hit ? 1 : 0;
+    }
+    if (p == 0)
+      goal_zero_tail(i, steps, T, a_dim, states_rec, actions_rec, goal.rewards, tid,
+                     64 * kRollMwWaves);
   }
   if constexpr (PROBE) {
     pr[6] += (long long)__builtin_amdgcn_s_memrealtime();
@@ -562,9 +644,10 @@ static size_t rollout_mw_bytes(int64_t n, int64_t T, int h1, int a_dim) {
 // [h0][64] f64 slice (dynamic) + sh1, spart, sword (static, 6.5 KB) within 160 KB of LDS
 static constexpr int kRollMwMaxH0 = 306;
 
-template <int ENV>
+template <int ENV, bool GOAL = false>
 static int rollout_mw_prepare() {
-  MEPOL_HIP(max_dynamic_lds<rollout_mlp_mw_kernel<ENV>>(kRollMwMaxH0 * 64 * (int)sizeof(double)));
+  MEPOL_HIP((max_dynamic_lds<rollout_mlp_mw_kernel<ENV, false, GOAL>>(
+      kRollMwMaxH0 * 64 * (int)sizeof(double))));
   return 0;
 }
 
@@ -577,7 +660,7 @@ static int rollout_mw_prepare() {
 // dedicated queue crashed the process at exit under rocprofv3: HIP's teardown of that queue
 // faulted inside libhsa-runtime64 after the profiler had shut its queue interception down,
 // profiles/r5/rollout_exit_crash.txt.)
-static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim) {
+static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim, bool goal = false) {
   const int np = (h1 + 63) / 64;
   const char* mw = getenv("MEPOL_ROLLOUT_MW");
   if (h0 > kRollMwMaxH0 || np * a_dim > 64 || (mw && mw[0] == '0')) return 0;
@@ -588,7 +671,11 @@ static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim) {
   const size_t lds = (size_t)h0 * 64 * sizeof(double);
   int per_cu = 0;
   hipError_t e;
-  if (env_id == 0) {
+  if (goal) {  // the goal-mode instance's own resources (env 1 only)
+    if (rollout_mw_prepare<1, true>()) return 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &per_cu, rollout_mlp_mw_kernel<1, false, true>, 64 * kRollMwWaves, lds);
+  } else if (env_id == 0) {
     if (rollout_mw_prepare<0>()) return 0;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_mlp_mw_kernel<0>,
                                                      64 * kRollMwWaves, lds);
@@ -630,7 +717,7 @@ extern "C" int mepol_rollout_mlp_workspace_size(int64_t n, int64_t T, int h0, in
   return 0;
 }
 
-template <int ENV>
+template <int ENV, bool GOAL = false>
 static hipError_t rollout_mw_launch(const double* W1, const double* b1, int h0,
                                     const double* W2t, const double* b2, int h1, const double* Wm,
                                     const double* bm, const double* log_std, int a_dim,
@@ -638,14 +725,91 @@ static hipError_t rollout_mw_launch(const double* W1, const double* b1, int h0,
                                     const double* noise, int64_t n, int64_t T, float* states_rec,
                                     float* actions_rec, double* visited, double* final_state,
                                     int np, int nw, unsigned long long* mail, int* err,
-                                    int* ticket, hipStream_t st) {
+                                    int* ticket, const GoalArgs& goal, hipStream_t st) {
   long long* probe = nullptr;
-  hipLaunchKernelGGL((rollout_mlp_mw_kernel<ENV>), dim3((unsigned)(n * np)),
+  hipLaunchKernelGGL((rollout_mlp_mw_kernel<ENV, false, GOAL>), dim3((unsigned)(n * np)),
                      dim3(64 * kRollMwWaves), (unsigned)((size_t)h0 * 64 * sizeof(double)), st,
                      W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T,
                      states_rec, actions_rec, visited, final_state, np, nw, mail, err, ticket,
-                     probe);
+                     probe, goal);
   return hipGetLastError();
+}
+
+// mepol_rollout_mlp_plan_info for mepol_rollout_goal: the goal-mode instance's own occupancy
+// decides its form.
+extern "C" int mepol_rollout_goal_plan_info(int64_t n, int h0, int h1, int a_dim,
+                                            int* workgroups_per_traj, int* k_chunks) {
+  if (n <= 0 || h0 <= 0 || h1 <= 0 || h0 > kRollMaxH || h1 > kRollMaxH || a_dim != 2 ||
+      !workgroups_per_traj || !k_chunks) {
+    set_error("mepol_rollout_goal_plan_info: bad arguments");
+    return kErrBadArg;
+  }
+  const int mw = rollout_use_mw(1, n, h0, h1, a_dim, true);
+  *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
+  *k_chunks = kRollChunks;  // both forms
+  return 0;
+}
+
+// mepol_rollout_mlp (goal == nullptr) and mepol_rollout_goal (env 1) behind their argument
+// checks: the same choice of form, workspace layout and launches, the kernels' GOAL instances
+// for the second.
+static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h0,
+                           const double* W2t, const double* b2, int h1, const double* Wm,
+                           const double* bm, const double* log_std, int a_dim,
+                           const double* init64, const float* init32, const double* noise,
+                           int64_t n, int64_t T, float* states_rec, float* actions_rec,
+                           double* visited, double* final_state, const GoalArgs* goal,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  const GoalArgs ga = goal ? *goal : GoalArgs{};
+  const int threads = ((h0 > h1 ? h0 : h1) + 63) / 64 * 64;
+  hipStream_t st = (hipStream_t)stream;
+  int* err = (int*)workspace;
+  if (err) MEPOL_HIP(hipMemsetAsync(err, 0, sizeof(int), st));  // whichever form runs
+  {
+    // several workgroups per trajectory when all of them can be resident at once
+    const int np = (h1 + 63) / 64, nw = threads / 64;
+    if (workspace && workspace_bytes >= rollout_mw_bytes(n, T, h1, a_dim) &&
+        rollout_use_mw(env_id, n, h0, h1, a_dim, goal != nullptr)) {
+      unsigned long long* mail = (unsigned long long*)((char*)workspace + 256);
+      int* ticket = err + 1;  // word 1 of the 256-byte header: the dispatch-order counter
+      MEPOL_HIP(hipMemsetAsync(ticket, 0, sizeof(int), st));
+      // every mail word starts as kMailEmpty (all ones)
+      MEPOL_HIP(hipMemsetAsync(mail, 0xff, (size_t)n * T * np * a_dim * 8, st));
+#define MEPOL_ROLL_MW(E, G)                                                                      \
+  rollout_mw_launch<E, G>(W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, \
+                          n, T, states_rec, actions_rec, visited, final_state, np, nw, mail, err, \
+                          ticket, ga, st)
+      const hipError_t e = goal          ? MEPOL_ROLL_MW(1, true)
+                           : env_id == 0 ? MEPOL_ROLL_MW(0, false)
+                                         : MEPOL_ROLL_MW(1, false);
+#undef MEPOL_ROLL_MW
+      if (e == hipSuccess) return 0;
+      (void)hipGetLastError();  // launch refused: the one-workgroup form
+    }
+  }
+  const dim3 g((unsigned)n);
+  // W2^T rows kept in LDS, the rest streamed: up to ~150 KB (MEPOL_ROLLOUT_KL caps it)
+  const char* klv = getenv("MEPOL_ROLLOUT_KL");
+  int KL = (int)((150 * 1024) / ((size_t)threads * sizeof(double)));
+  if (klv) KL = std::min(KL, atoi(klv));
+  KL = std::max(0, std::min(KL, h0));
+  const size_t lds = (size_t)KL * threads * sizeof(double);
+#define MEPOL_ROLL(E, U, G)                                                                       \
+  do {                                                                                            \
+    MEPOL_HIP((max_dynamic_lds<rollout_mlp_kernel<E, U, G>>(150 * 1024)));                        \
+    hipLaunchKernelGGL((rollout_mlp_kernel<E, U, G>), g, dim3(threads), lds, st, W1, b1, h0, W2t, \
+                       b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T, states_rec,   \
+                       actions_rec, visited, final_state, KL, ga);                                \
+  } while (0)
+  if (goal)
+    MEPOL_ROLL(1, 8, true);
+  else if (env_id == 0)
+    MEPOL_ROLL(0, 8, false);
+  else
+    MEPOL_ROLL(1, 8, false);
+#undef MEPOL_ROLL
+  MEPOL_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int mepol_rollout_mlp(int env_id, const double* W1, const double* b1, int h0,
@@ -665,51 +829,53 @@ extern "C" int mepol_rollout_mlp(int env_id, const double* W1, const double* b1,
               kRollMaxA);
     return kErrBadArg;
   }
-  const int threads = ((h0 > h1 ? h0 : h1) + 63) / 64 * 64;
-  hipStream_t st = (hipStream_t)stream;
-  int* err = (int*)workspace;
-  if (err) MEPOL_HIP(hipMemsetAsync(err, 0, sizeof(int), st));  // whichever form runs
-  {
-    // several workgroups per trajectory when all of them can be resident at once
-    const int np = (h1 + 63) / 64, nw = threads / 64;
-    if (workspace && workspace_bytes >= rollout_mw_bytes(n, T, h1, a_dim) &&
-        rollout_use_mw(env_id, n, h0, h1, a_dim)) {
-      unsigned long long* mail = (unsigned long long*)((char*)workspace + 256);
-      int* ticket = err + 1;  // word 1 of the 256-byte header: the dispatch-order counter
-      MEPOL_HIP(hipMemsetAsync(ticket, 0, sizeof(int), st));
-      // every mail word starts as kMailEmpty (all ones)
-      MEPOL_HIP(hipMemsetAsync(mail, 0xff, (size_t)n * T * np * a_dim * 8, st));
-      const hipError_t e =
-          env_id == 0
-              ? rollout_mw_launch<0>(W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64,
-                                     init32, noise, n, T, states_rec, actions_rec, visited,
-                                     final_state, np, nw, mail, err, ticket, st)
-              : rollout_mw_launch<1>(W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64,
-                                     init32, noise, n, T, states_rec, actions_rec, visited,
-                                     final_state, np, nw, mail, err, ticket, st);
-      if (e == hipSuccess) return 0;
-      (void)hipGetLastError();  // launch refused: the one-workgroup form
-    }
+  return rollout_mlp_run(env_id, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32,
+                         noise, n, T, states_rec, actions_rec, visited, final_state, nullptr,
+                         workspace, workspace_bytes, stream);
+}
+
+// The goal-mode workspace: the same layout as mepol_rollout_mlp's, sized by the goal-mode
+// kernel's own occupancy.
+extern "C" int mepol_rollout_goal_workspace_size(int env_id, int64_t n, int64_t T, int h0, int h1,
+                                                 int a_dim, size_t* bytes) {
+  if (n < 0 || T < 0 || h0 <= 0 || h1 <= 0 || a_dim <= 0 || a_dim > kRollMaxA || env_id < 0 ||
+      env_id > 1 || !bytes) {
+    set_error("mepol_rollout_goal_workspace_size: bad arguments");
+    return kErrBadArg;
   }
-  const dim3 g((unsigned)n);
-  // W2^T rows kept in LDS, the rest streamed: up to ~150 KB (MEPOL_ROLLOUT_KL caps it)
-  const char* klv = getenv("MEPOL_ROLLOUT_KL");
-  int KL = (int)((150 * 1024) / ((size_t)threads * sizeof(double)));
-  if (klv) KL = std::min(KL, atoi(klv));
-  KL = std::max(0, std::min(KL, h0));
-  const size_t lds = (size_t)KL * threads * sizeof(double);
-#define MEPOL_ROLL(E, U)                                                                          \
-  do {                                                                                            \
-    MEPOL_HIP((max_dynamic_lds<rollout_mlp_kernel<E, U>>(150 * 1024)));                           \
-    hipLaunchKernelGGL((rollout_mlp_kernel<E, U>), g, dim3(threads), lds, st, W1, b1, h0, W2t, b2, \
-                       h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T, states_rec,       \
-                       actions_rec, visited, final_state, KL);                                    \
-  } while (0)
-  if (env_id == 0)
-    MEPOL_ROLL(0, 8);
-  else
-    MEPOL_ROLL(1, 8);
-#undef MEPOL_ROLL
-  MEPOL_CHECK_LAUNCH();
+  if (env_id != 1) {
+    set_error("mepol_rollout_goal: only GridWorld (env_id 1) has a goal mode");
+    return kErrUnsupported;
+  }
+  *bytes = (n > 0 && rollout_use_mw(1, n, h0, h1, a_dim, true)) ? rollout_mw_bytes(n, T, h1, a_dim)
+                                                                : 256;
   return 0;
+}
+
+extern "C" int mepol_rollout_goal(int env_id, const double* W1, const double* b1, int h0,
+                                  const double* W2t, const double* b2, int h1, const double* Wm,
+                                  const double* bm, const double* log_std, int a_dim,
+                                  const float* init32, const double* noise, int64_t n, int64_t T,
+                                  float goal_x, float goal_y, double radius, float* states_rec,
+                                  float* actions_rec, float* rewards_rec, int32_t* len_out,
+                                  int32_t* done_out, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  if (n <= 0 || T <= 0) return 0;
+  if (env_id < 0 || env_id > 1 || h0 <= 0 || h1 <= 0 || h0 > kRollMaxH || h1 > kRollMaxH ||
+      a_dim != 2 || T > INT32_MAX || !init32 || !W1 || !b1 || !W2t || !b2 || !Wm || !bm ||
+      !log_std || !noise || !states_rec || !actions_rec || !rewards_rec || !len_out ||
+      !done_out || !(goal_x == goal_x) || !(goal_y == goal_y) || !(radius >= 0.0) ||
+      (workspace && workspace_bytes < sizeof(int))) {
+    set_error("mepol_rollout_goal: bad arguments (hidden <= %d, a_dim = 2, radius >= 0)",
+              kRollMaxH);
+    return kErrBadArg;
+  }
+  if (env_id != 1) {
+    set_error("mepol_rollout_goal: only GridWorld (env_id 1) has a goal mode");
+    return kErrUnsupported;
+  }
+  const GoalArgs goal{goal_x, goal_y, radius, rewards_rec, len_out, done_out};
+  return rollout_mlp_run(1, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, nullptr, init32,
+                         noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
+                         workspace_bytes, stream);
 }

@@ -1,6 +1,7 @@
 from .gridworld import GridWorldContinuous
 from .mountain_car import MountainCarContinuous
 from .spaces import Box
-from .wrappers import ErgodicEnv, unwrap
+from .wrappers import CustomRewardEnv, ErgodicEnv, GridGoal, unwrap
 
-__all__ = ["GridWorldContinuous", "MountainCarContinuous", "Box", "ErgodicEnv", "unwrap"]
+__all__ = ["GridWorldContinuous", "MountainCarContinuous", "Box", "ErgodicEnv",
+           "CustomRewardEnv", "GridGoal", "unwrap"]

@@ -1,7 +1,11 @@
 """What the Gaussian policy's HIP kernel path takes, and its layer chain, each written once for
 get_log_p (policy.py), the graph loop (algorithms/device_loop.py), TRPO's Fisher products
 (algorithms/trpo.py) and the one-launch rollouts (algorithms/mepol.py).  The gates stay with
-those consumers and add what only they know (row floors, dtypes, the optimizer)."""
+those consumers and add what only they know (row floors, dtypes, the optimizer); the gate of
+TRPO's goal sampler (goal_sampler) is here because it joins an env with a policy."""
+import os
+
+import torch
 import torch.nn as nn
 
 from . import ops
@@ -14,6 +18,7 @@ MULTILAYER_MIN, MULTILAYER_MAX = 3, 6  # hidden layers of the deep chain (2 L + 
 ROLLOUT_MAX_WIDTH = 512                # one-launch rollouts: csrc/envs.hip, csrc/rollout_deep.hip
 ROLLOUT_MAX_ACTIONS = 8
 ROLLOUT_FEATURES = 2
+GRIDWORLD_DEFAULTS = (6, 0.2, 2.5)     # (dim, max_delta, wall_width) the kernels' GridWorld has
 
 TWO_LAYER, MULTILAYER = "two-layer", "multilayer"
 
@@ -73,3 +78,31 @@ def hidden_backward(dz, x, Ws, hs, dW_out=None, db_out=None, dz_out=None, ws_wgr
     dW[0], _ = ops.layer_backward(dz, hs[0], x, ws=ws_layer, dW_out=_at(dW_out, 0),
                                   db_out=layer_db_out)
     return dW, db
+
+
+def goal_sampler(env, policy):
+    """(goal, layers) when TRPO's sampler (algorithms/trpo.py collect_sample_batch) takes the
+    one-launch goal rollout (ops.rollout_goal), else None: an f64 policy on the GPU that
+    algorithms.mepol._rollout_mlp_layers accepts (2 -> [h0, h1] -> a ReLU MLP, widths <= 512),
+    two actions, and a CustomRewardEnv directly over GridWorldContinuous whose reward is a
+    GridGoal.  goal is that GridGoal (its f32 goal and radius are the kernel's arguments), layers
+    = ((W1, b1), (W2, b2)).  MEPOL_TRPO_SAMPLER=host turns the kernel path off."""
+    from .algorithms.mepol import _rollout_mlp_layers
+    from .envs.gridworld import GridWorldContinuous
+    from .envs.wrappers import CustomRewardEnv, GridGoal
+
+    if os.environ.get("MEPOL_TRPO_SAMPLER", "kernel") == "host":
+        return None
+    if not (type(env) is CustomRewardEnv and type(env.env) is GridWorldContinuous
+            and isinstance(env.get_reward, GridGoal)):
+        return None
+    # the kernel's GridWorld is the default one: its size, step and walls are constants there
+    if (env.env.dim, env.env.max_delta, env.env.wall_width) != GRIDWORLD_DEFAULTS:
+        return None
+    log_std = getattr(policy, "log_std", None)
+    if (log_std is None or not log_std.is_cuda or log_std.dtype != torch.float64
+            or getattr(policy, "action_dim", None) != 2
+            or policy.mean.weight.dtype != torch.float64):
+        return None
+    layers = _rollout_mlp_layers(policy, env.num_features, 2)
+    return None if layers is None else (env.get_reward, layers)

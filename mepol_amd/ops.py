@@ -780,6 +780,129 @@ def rollout_mlp_plan(n, h0, h1, a_dim):
     return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
 
 
+def rollout_goal_plan(n, h0, h1, a_dim=2):
+    """rollout_mlp_plan for rollout_goal: the form the goal-mode kernel's own occupancy gives."""
+    wg, kc = ctypes.c_int(), ctypes.c_int()
+    call("mepol_rollout_goal_plan_info", n, h0, h1, a_dim, ctypes.byref(wg), ctypes.byref(kc))
+    return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
+
+
+def rollout_goal(W1, b1, W2, b2, Wm, bm, log_std, init, noise, goal_xy, radius, states_rec,
+                 actions_rec, rewards_rec, len_out, done_out, env_id=1, defer_check=False):
+    """rollout_mlp on GridWorld (env_id 1) with early termination at a goal: a trajectory ends at
+    the first step whose f32 state is within `radius` of goal_xy (reward 1, done), or after T
+    steps.  Fills states_rec [n,T+1,2], actions_rec [n,T,2], rewards_rec [n,T] (f32, zeros behind
+    each episode's end), len_out and done_out [n] int32; the buffers need no clearing.
+
+    The error word is handled as rollout_mlp does: on a multi-workgroup refusal, warn and re-run
+    the one-workgroup form (the same bits).  defer_check=True leaves that to the caller: the
+    return value is (err, rerun), a device int32 [1] view of the word and the re-run, so the word
+    can be read together with the caller's own results in one synchronisation."""
+    _require_device(init, noise, states_rec, actions_rec, rewards_rec, len_out, done_out, W1, b1,
+                    W2, b2, Wm, bm, log_std)
+    T, n, a_dim = noise.shape
+    h0, h1 = W1.shape[0], W2.shape[0]
+    if (tuple(W1.shape) != (h0, 2) or tuple(W2.shape) != (h1, h0) or tuple(Wm.shape) != (a_dim, h1)
+            or tuple(init.shape) != (n, 2) or tuple(states_rec.shape) != (n, T + 1, 2)
+            or tuple(actions_rec.shape) != (n, T, a_dim) or tuple(rewards_rec.shape) != (n, T)
+            or len_out.numel() != n or done_out.numel() != n):
+        raise ValueError("rollout_goal: tensor shapes do not fit the policy / batch")
+    if (any(t.dtype != torch.float64 for t in (W1, b1, W2, b2, Wm, bm, log_std, noise))
+            or any(t.dtype != torch.float32 for t in (init, states_rec, actions_rec, rewards_rec))
+            or len_out.dtype != torch.int32 or done_out.dtype != torch.int32
+            or not all(t.is_contiguous() for t in (states_rec, actions_rec, rewards_rec, len_out,
+                                                   done_out))):
+        raise ValueError("rollout_goal: f64 policy / noise, f32 contiguous records, int32 len / done")
+    W2t = W2.t().contiguous()
+    # (contiguous copies stay referenced until the launch is queued)
+    W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
+                                                                          log_std, init, noise))
+    ws = _ws_or_cached(None, init.device, "rollout", "rollout_goal", env_id, n, T, h0, h1, a_dim)
+    gx, gy = (float(v) for v in goal_xy)
+    args = (env_id, ptr(W1), ptr(b1), h0, ptr(W2t), ptr(b2), h1, ptr(Wm), ptr(bm), ptr(log_std),
+            a_dim, ptr(init), ptr(noise), n, T, gx, gy, float(radius), ptr(states_rec),
+            ptr(actions_rec), ptr(rewards_rec), ptr(len_out), ptr(done_out))
+    keep = (W1, b1, W2t, b2, Wm, bm, log_std, init, noise)
+    call("mepol_rollout_goal", *args, ptr(ws), ws.numel(), _stream())
+
+    def rerun(_keep=keep):
+        import warnings
+
+        warnings.warn("mepol_rollout_goal: workgroups of a trajectory were not co-resident; "
+                      "re-ran the one-workgroup form")
+        call("mepol_rollout_goal", *args, None, 0, _stream())
+
+    err = ws[:4].view(torch.int32)
+    if defer_check:
+        return err, rerun
+    if n > 0 and T > 0 and int(err[0].item()) != 0:
+        rerun()
+    return None
+
+
+def traj_budget(lens, dones, budget):
+    """The step budget over a parallel batch (mepol_traj_budget): trajectories in index order until
+    `budget` steps are kept, the last one cut.  lens, dones: int32 [n] on the device.  Returns
+    (len_out int32 [n], done_out int32 [n], offsets int64 [n+1], meta int64 [2] = {trajectories
+    used, steps kept}), all on the device."""
+    _require_device(lens, dones)
+    n = lens.numel()
+    if lens.dtype != torch.int32 or dones.dtype != torch.int32 or dones.numel() != n:
+        raise ValueError("traj_budget: int32 lens and dones of one size")
+    dev = lens.device
+    len_out = torch.empty(n, dtype=torch.int32, device=dev)
+    done_out = torch.empty(n, dtype=torch.int32, device=dev)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    meta = torch.zeros(2, dtype=torch.int64, device=dev)
+    call("mepol_traj_budget", ptr(lens.contiguous()), ptr(dones.contiguous()), n, int(budget),
+         ptr(len_out), ptr(done_out), ptr(offsets), ptr(meta), _stream())
+    return len_out, done_out, offsets, meta
+
+
+def gae(rewards, values, lens, dones, offsets, n_out, gamma, lambd, states_rec, actions_rec):
+    """Targets, GAE advantages and the packed batch of ragged trajectories (mepol_gae).  rewards
+    [n,T] f32, values [n,T+1] f64, lens / dones int32 [n], offsets int64 [n+1] (traj_budget's),
+    n_out = offsets[n] (a host int), states_rec [n,T+1,nf] and actions_rec [n,T,a] f32.  Returns
+    (targets [n_out], adv [n_out], states [n_out,nf], actions [n_out,a]), all f64."""
+    _require_device(rewards, values, lens, dones, offsets, states_rec, actions_rec)
+    n, T = rewards.shape
+    nf, a = states_rec.shape[2], actions_rec.shape[2]
+    if (tuple(values.shape) != (n, T + 1) or tuple(states_rec.shape) != (n, T + 1, nf)
+            or tuple(actions_rec.shape) != (n, T, a) or lens.numel() != n or dones.numel() != n
+            or offsets.numel() != n + 1):
+        raise ValueError("gae: tensor shapes do not fit the batch")
+    if (rewards.dtype != torch.float32 or values.dtype != torch.float64
+            or states_rec.dtype != torch.float32 or actions_rec.dtype != torch.float32
+            or lens.dtype != torch.int32 or dones.dtype != torch.int32
+            or offsets.dtype != torch.int64):
+        raise ValueError("gae: f32 rewards / records, f64 values, int32 lens / dones, int64 offsets")
+    rewards, values, lens, dones, offsets, states_rec, actions_rec = (
+        t.contiguous() for t in (rewards, values, lens, dones, offsets, states_rec, actions_rec))
+    dev = rewards.device
+    n_out = int(n_out)
+    f64 = dict(dtype=torch.float64, device=dev)
+    targets, adv = torch.empty(n_out, **f64), torch.empty(n_out, **f64)
+    states, actions = torch.empty((n_out, nf), **f64), torch.empty((n_out, a), **f64)
+    call("mepol_gae", ptr(rewards), ptr(values), ptr(lens), ptr(dones), ptr(offsets), n, T, n_out,
+         float(gamma), float(lambd), ptr(states_rec), nf, ptr(actions_rec), a, ptr(targets),
+         ptr(adv), ptr(states), ptr(actions), _stream())
+    return targets, adv, states, actions
+
+
+def standardize(x, out=None):
+    """(x - mean) / population std of an f64 vector on the device (mepol_standardize): the same
+    bits on every call; a zero std gives non-finite values, as numpy does."""
+    _require_device(x, out)
+    if x.dim() != 1 or x.dtype != torch.float64 or not x.is_contiguous():
+        raise ValueError("standardize: a contiguous f64 vector is needed")
+    n = x.numel()
+    res = out if out is not None else torch.empty_like(x)
+    assert res.shape == x.shape and res.dtype == x.dtype and res.is_contiguous()
+    ws = _ws_or_cached(None, x.device, "standardize", "standardize", n)
+    call("mepol_standardize", ptr(x), n, ptr(res), ptr(ws), ws.numel(), _stream())
+    return res
+
+
 def memcpy_async(dst, src):
     """dst <- src (same byte size; device or pinned host tensors), ordered on the current
     stream; inside a graph capture this is a memcpy node."""

@@ -347,7 +347,12 @@ int mepol_policy_forward_plan_info(int64_t n, int in_features, int hidden0, int 
  * h1 = relu(x W1^T + b1) from dz2 [n, k] and W2t = W2^T [h0, k] (dh1 = dz2 W2 stays on chip,
  * masked by h1 > 0 from the forward's h1 [n, h0]).  k even, in_features <= 63, dz2 and W2t
  * 16-byte aligned; workspace from mepol_dh1_layer1_workspace_size.  Replaces the dh1
- * torch.mm + threshold_backward + dW1/db1 reductions of loss.backward() (mepol.py:278). */
+ * torch.mm + threshold_backward + dW1/db1 reductions of loss.backward() (mepol.py:278).
+ * Precondition, for this and the two forms below: every element of x is finite.  The kernel
+ * removes the rows and columns of [x | 1] that lie past n and in_features by a product with 0,
+ * not a select, and those positions re-read the last row and the last column of x: an inf or
+ * nan there would reach rows of dW1 and db1 it has no path to.  dz2, W2 and h1 may hold
+ * non-finite values; they reach only the outputs that depend on them. */
 int mepol_dh1_layer1_workspace_size(int64_t n, int hidden0, int in_features, size_t* bytes);
 int mepol_dh1_layer1_backward(const double* dz2, int64_t n, int k, const double* W2t, int hidden0,
                               const double* h1, const double* x, int in_features, double* dW1,
@@ -376,6 +381,19 @@ int mepol_weight_grad_workspace_size(int64_t n, int out_features, int in_feature
 int mepol_weight_grad(const double* dy, int64_t n, int out_features, const double* x,
                       int in_features, double* dW, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/* Host only (no GPU call): the launch plan mepol_weight_grad takes at these sizes.  *nob, *nib:
+ * blocks of 64 output rows and of 80 input columns; *fol: 16-row fragments of the last o-block
+ * (1 .. 4); *Sf, *Ss: K-slices of the full o-blocks (0 when nob == 1) and of the last one;
+ * *rows_f, *rows_s: rows per slice of each kind (multiples of 4); *grid8: workgroups per XCD
+ * (the grid is 8 * grid8).  fend, send, fbase, sbase [8]: workgroup b is entry j = b / 8 of XCD
+ * x = b % 8; j < fend[x] is the full tile j % ((nob - 1) nib) of slice fbase[x] + j / ((nob - 1)
+ * nib), fend[x] <= j < send[x] the short tile (j - fend[x]) % nib of slice sbase[x] +
+ * (j - fend[x]) / nib, and j >= send[x] has no work.  The workspace holds [Sf][64 (nob - 1)][in]
+ * then [Ss][out - 64 (nob - 1)][in] doubles.  n, out_features, in_features > 0. */
+int mepol_weight_grad_plan_info(int64_t n, int out_features, int in_features, int* nob, int* nib,
+                                int* fol, int* Sf, int* Ss, int64_t* rows_f, int64_t* rows_s,
+                                int* grid8, int* fend, int* send, int* fbase, int* sbase);
 
 /* Hidden layer on the f64 matrix cores: C = act(A B^T + bias), A [n, k] (row stride lda),
  * B [m, k] (ldb), bias [m] (nullable), C [n, m] (ldc); act = ReLU when relu != 0.  k, lda, ldb

@@ -363,7 +363,10 @@ __global__ __launch_bounds__(l1b::P::kThreads) void dh1_layer1_bwd_kernel(
               on = ((hv[j][i][q] >> fr) & 1u) != 0;
             else
               on = hv[j][i][q] > 0.0;
-            const double dz = (on && c < M) ? acc[i][j][q] : 0.0;
+            // (a row past N has acc = 0 x W2: nan where W2 holds an inf, and its clamped mask
+            // is the last row's: the row test keeps that nan out of the column's sums)
+            const bool rin = row0 + wave * FR * 16 + i * 16 + 4 * q + g < N;
+            const double dz = (on && rin && c < M) ? acc[i][j][q] : 0.0;
 #pragma unroll
             for (int h = 0; h < NH; ++h)
               dacc[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(dz, xb[i][q][h], dacc[h], 0, 0, 0);

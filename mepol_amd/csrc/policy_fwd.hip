@@ -406,7 +406,12 @@ __global__ __launch_bounds__(64 * zh::NW) __attribute__((amdgpu_waves_per_eu(zh:
 #pragma unroll
   for (int u = 0; u < FI; ++u) {
     const int c = col0 + 16 * u + fr;
-    b2v[u] = c < H2 ? b2[c] : 0.0;
+    // A column past H2 holds the clamped load's copy of column H2 - 1 in acc.  Its Wm is 0, but
+    // 0 x inf is nan: with an infinite z2 in the last column every mu of the row became nan
+    // instead of that infinity.  A bias of -inf makes relu(acc + b2v) exactly 0 there whatever
+    // acc is (finite and -inf: -inf, +inf and nan: nan, and fmax(nan, 0) = 0), with no select in
+    // the action loop.
+    b2v[u] = c < H2 ? b2[c] : -HUGE_VAL;
 #pragma unroll
     for (int t = 0; t < FO; ++t)
 #pragma unroll

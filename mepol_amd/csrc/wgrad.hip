@@ -285,6 +285,27 @@ extern "C" int mepol_weight_grad_workspace_size(int64_t n, int out_features, int
   return 0;
 }
 
+// Host only (no GPU call): the launch plan of mepol_weight_grad at these sizes.
+extern "C" int mepol_weight_grad_plan_info(int64_t n, int out_features, int in_features, int* nob,
+                                           int* nib, int* fol, int* Sf, int* Ss, int64_t* rows_f,
+                                           int64_t* rows_s, int* grid8, int* fend, int* send,
+                                           int* fbase, int* sbase) {
+  if (n <= 0 || out_features <= 0 || in_features <= 0 || !nob || !nib || !fol || !Sf || !Ss ||
+      !rows_f || !rows_s || !grid8 || !fend || !send || !fbase || !sbase) {
+    mepol::set_error("mepol_weight_grad_plan_info: bad arguments (n, out_features, in_features "
+                     "positive; every output non-null)");
+    return mepol::kErrBadArg;
+  }
+  const mepol::wgrad::Plan p = mepol::wgrad::plan_for(n, out_features, in_features);
+  *nob = p.nob, *nib = p.nib, *fol = p.fol, *Sf = p.Sf, *Ss = p.Ss;
+  *rows_f = p.rows_f, *rows_s = p.rows_s, *grid8 = p.grid8;
+  for (int x = 0; x < 8; ++x) {
+    fend[x] = p.m.fend[x], send[x] = p.m.send[x];
+    fbase[x] = p.m.fbase[x], sbase[x] = p.m.sbase[x];
+  }
+  return 0;
+}
+
 extern "C" int mepol_weight_grad(const double* dy, int64_t n, int out_features, const double* x,
                                  int in_features, double* dW, void* workspace,
                                  size_t workspace_bytes, void* stream) {

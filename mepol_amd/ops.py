@@ -477,6 +477,22 @@ def weight_grad_workspace(n, out_features, in_features, device):
     return _own_workspace(device, "weight_grad", n, out_features, in_features)
 
 
+def weight_grad_plan(n, out_features, in_features):
+    """The launch plan of weight_grad at these sizes (host only: mepol_weight_grad_plan_info):
+    {"nob", "nib", "fol", "Sf", "Ss", "rows_f", "rows_s", "grid8"} and the slice -> XCD map
+    "fend", "send", "fbase", "sbase" (lists of 8), as csrc/wgrad.hip's Plan describes them."""
+    ints = {k: ctypes.c_int() for k in ("nob", "nib", "fol", "Sf", "Ss", "grid8")}
+    rows = {k: ctypes.c_int64() for k in ("rows_f", "rows_s")}
+    maps = {k: (ctypes.c_int * 8)() for k in ("fend", "send", "fbase", "sbase")}
+    call("mepol_weight_grad_plan_info", n, out_features, in_features,
+         *[ctypes.byref(ints[k]) for k in ("nob", "nib", "fol", "Sf", "Ss")],
+         ctypes.byref(rows["rows_f"]), ctypes.byref(rows["rows_s"]), ctypes.byref(ints["grid8"]),
+         *[maps[k] for k in ("fend", "send", "fbase", "sbase")])
+    plan = {k: v.value for k, v in {**ints, **rows}.items()}
+    plan.update({k: list(v) for k, v in maps.items()})
+    return plan
+
+
 def weight_grad(dy, x, out=None, ws=None):
     """dW = dy^T x for dy [n, out] and x [n, in] (f64, row-major): the weight gradient of a
     Linear layer over a tall batch (csrc/wgrad.hip: split-K on the f64 matrix cores, fixed-order

@@ -216,3 +216,98 @@ def optim_step(kind, params, grads, exp_avg, exp_avg_sq, scalars, snapshot=None)
                 lr, alpha, eps = sc[1:4]
                 v[...] = v * alpha + (1.0 - alpha) * (g * g)
                 p[...] = p + (-lr) * (g / (np.sqrt(v) + eps))
+
+
+# ---------------------------------------------------------------------------------------------
+# The f64 matrix-core kernels (csrc/gemm.hip, wgrad.hip, policy_fwd.hip) in plain f64 numpy.
+# Every ReLU and mask is a select, as in the kernels: a nan that is masked off (or a nan
+# pre-activation) gives 0.
+# ---------------------------------------------------------------------------------------------
+def _sel(mask, v):
+    return np.where(mask, v, 0.0)
+
+
+def _gt0(v):
+    with np.errstate(invalid="ignore"):
+        return v > 0.0
+
+
+def _pack_mask(on):
+    """[n, h0] bools -> [n, ceil(h0 / 16)] int16 words, bit b of word w = on[:, 16 w + b]."""
+    n, h0 = on.shape
+    mw = (h0 + 15) // 16
+    bits = np.zeros((n, mw * 16), np.uint16)
+    bits[:, :h0] = on
+    words = (bits.reshape(n, mw, 16) << np.arange(16, dtype=np.uint16)).sum(axis=2)
+    return words.astype(np.uint16).view(np.int16)
+
+
+def _unpack_mask(words, h0):
+    w = words.numpy().view(np.uint16)
+    bits = (w[:, :, None] >> np.arange(16, dtype=np.uint16)) & 1
+    return bits.reshape(w.shape[0], -1)[:, :h0].astype(bool)
+
+
+def _scratch(*_):
+    return torch.empty(1, dtype=torch.uint8)
+
+
+dh1_layer1_workspace = weight_grad_workspace = hidden_backward_workspace = _scratch
+
+
+def h1_mask_buffer(n, hidden0, device):
+    return torch.empty((n, (hidden0 + 15) // 16), dtype=torch.int16)
+
+
+def gemm_nt(A, B, bias=None, relu=False, out=None, variant=0):
+    with np.errstate(invalid="ignore"):
+        v = _np(A) @ _np(B).T
+        if bias is not None:
+            v = v + _np(bias)
+    if relu:
+        v = _sel(_gt0(v), v)
+    return _into(out, v)
+
+
+def policy_forward(x, W1, b1, W2, b2, Wm, bm, log_std, act, h1_out=None, z2_out=None,
+                   mu_out=None, logp_out=None, mask_out=None, row_tile=0):
+    with np.errstate(invalid="ignore", over="ignore"):
+        pre = _np(x) @ _np(W1).T + _np(b1)
+        h1 = _sel(_gt0(pre), pre)
+        z2 = h1 @ _np(W2).T
+        pre2 = z2 + _np(b2)
+        mu = _sel(_gt0(pre2), pre2) @ _np(Wm).T + _np(bm)
+        ls = _np(log_std)
+        sigma = np.exp(ls) + _STD_EPS
+        d = _np(act) - mu
+        logp = (-0.5 * (_LOG2PI + 2.0 * ls + d * d / (sigma * sigma))).sum(axis=1)
+    if mask_out is not None:
+        mask_out.copy_(torch.as_tensor(_pack_mask(h1 > 0.0)))
+    return _into(h1_out, h1), _into(z2_out, z2), _into(mu_out, mu), _into(logp_out, logp)
+
+
+def dh1_layer1_backward(dz2, W2t, h1, x, ws=None, dW_out=None, db_out=None, mask=None, w2=None):
+    # (a copy in W2t's layout: BLAS sums a transposed view in another order)
+    Wt = np.ascontiguousarray(_np(w2).T) if w2 is not None else _np(W2t)
+    on = _unpack_mask(mask, Wt.shape[0]) if mask is not None else _gt0(_np(h1))
+    with np.errstate(invalid="ignore", over="ignore"):
+        dz1 = _sel(on, _np(dz2) @ Wt.T)
+        return _into(dW_out, dz1.T @ _np(x)), _into(db_out, dz1.sum(axis=0))
+
+
+def weight_grad(dy, x, out=None, ws=None):
+    with np.errstate(invalid="ignore", over="ignore"):
+        return _into(out, _np(dy).T @ _np(x))
+
+
+def hidden_backward(dz_out, W, h_in, ws=None, dz_out_buf=None, db_out=None):
+    with np.errstate(invalid="ignore", over="ignore"):
+        dz = _sel(_gt0(_np(h_in)), _np(dz_out) @ _np(W))
+        return _into(dz_out_buf, dz), _into(db_out, dz.sum(axis=0))
+
+
+def hidden_tangent(t_in, h_in, W, dW, db, mask_src, mask_bias=None, out=None, variant=0):
+    with np.errstate(invalid="ignore", over="ignore"):
+        pre = _np(mask_src) + (_np(mask_bias) if mask_bias is not None else 0.0)
+        v = _np(t_in) @ _np(W).T + _np(h_in) @ _np(dW).T + _np(db)
+    return _into(out, _sel(_gt0(pre), v))

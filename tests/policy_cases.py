@@ -98,13 +98,16 @@ def _sigma_terms(log_std):
 
 
 def _relu_in(z, bz):
-    """x = relu(z + bz) with its bound: one rounding of the sum when there is a bz, none else."""
+    """x = relu(z + bz) with its bound: one rounding of the sum when there is a bz, none else.
+    The relu is the select [pre > 0] ? pre : 0, as the kernels' fmax(pre, 0.0) and their masks
+    are: a nan pre-activation gives 0 (tests/gemm_cases.py has such inputs; no case here does)."""
     pre = ld(z) + ld(bz) if bz is not None else ld(z)
-    x = np.maximum(pre, 0)
+    with np.errstate(invalid="ignore"):
+        x = np.where(pre > 0, pre, 0)
     return pre, x, (U0 if bz is not None else 0 * U0)
 
 
-def head_fwd_ref(z, bz, Wm, bm, log_std, act):
+def head_fwd_ref(z, bz, Wm, bm, log_std, act, dz_in=None):
     """mu_ia = sum_c x_ic Wm_ac + bm_a, x = relu(z + bz): H + 1 terms.  Each product carries x's
     rounding (with a bz) and its own (none under fma: looser, never tighter), then at most H adds
     whatever the order (16 lanes of strided columns, a 4-step exchange, the bias last): m = H + 2,
@@ -113,7 +116,10 @@ def head_fwd_ref(z, bz, Wm, bm, log_std, act):
     one add; the f64 constant is within u0 log 2pi of log 2pi), q_a = d^2 inv_a, d = act - mu^:
     |d^ - d| <= bmu + u0 |d|, the square doubles it and rounds once, the product with inv adds
     inv's relative bound and one rounding; t_a rounds once; the product by -0.5 is exact; the A
-    terms are summed in any order (A - 1 adds; A = 1: the sum is the term)."""
+    terms are summed in any order (A - 1 adds; A = 1: the sum is the term).
+    dz_in [n, H]: the bound of a z that was itself computed (tests/gemm_cases.py: the z2 of
+    policy_forward).  The sum with bz and the relu move a value by no more than their input
+    moved, so mu's bound grows by sum_c dz_in_ic |Wm_ac|, and logp's follows through bmu."""
     n, H = z.shape
     A = Wm.shape[0]
     pre, x, ux = _relu_in(z, bz)
@@ -121,6 +127,8 @@ def head_fwd_ref(z, bz, Wm, bm, log_std, act):
     mu = _mm(x, W.T) + ld(bm)
     Amu = _mmb(x, np.abs(W).T) + np.abs(ld(bm))
     bmu = (H + 2) * U0 * Amu * SLACK if bz is not None else (H + 1) * U0 * Amu * SLACK
+    if dz_in is not None:
+        bmu = bmu + _mmb(dz_in, np.abs(W).T) * SLACK
     s = _sigma_terms(log_std)
     K = LOG2PI + 2 * s.ls
     bK = U0 * (np.abs(K) + LOG2PI)

@@ -352,7 +352,9 @@ int mepol_policy_forward_plan_info(int64_t n, int in_features, int hidden0, int 
  * removes the rows and columns of [x | 1] that lie past n and in_features by a product with 0,
  * not a select, and those positions re-read the last row and the last column of x: an inf or
  * nan there would reach rows of dW1 and db1 it has no path to.  dz2, W2 and h1 may hold
- * non-finite values; they reach only the outputs that depend on them. */
+ * non-finite values; they reach only the outputs that depend on them.  (The register-fed form
+ * of the mask calls, mepol_dh1_layer1_plan_info, removes them with a select; the precondition
+ * holds for the op whichever kernel runs.) */
 int mepol_dh1_layer1_workspace_size(int64_t n, int hidden0, int in_features, size_t* bytes);
 int mepol_dh1_layer1_backward(const double* dz2, int64_t n, int k, const double* W2t, int hidden0,
                               const double* h1, const double* x, int in_features, double* dW1,
@@ -365,12 +367,44 @@ int mepol_dh1_layer1_backward_masked(const double* dz2, int64_t n, int k, const 
                                      int in_features, double* dW1, double* db1, void* workspace,
                                      size_t workspace_bytes, void* stream);
 /* The masked form with the second Linear's weight as stored, W2 [k][hidden0] (hidden0 even,
- * 16-B aligned), instead of W2^T: the kernel transposes its k-tiles on the way into LDS, so the
- * caller needs no W2^T copy per optimizer step (ABI 4).  Identical results. */
+ * 16-B aligned), instead of W2^T: the kernel transposes its k-tiles on the way into LDS (the
+ * register-fed form reads rows k and k + 1 of W2 per fragment instead), so the caller needs no
+ * W2^T copy per optimizer step (ABI 4).  Identical results. */
 int mepol_dh1_layer1_backward_w2(const double* dz2, int64_t n, int k, const double* W2,
                                  int hidden0, const uint16_t* h1_mask, const double* x,
                                  int in_features, double* dW1, double* db1, void* workspace,
                                  size_t workspace_bytes, void* stream);
+
+/* The two mask forms with the kernel chosen by the caller.  w2 == 0: W is W2^T [hidden0][k];
+ * w2 != 0: W is W2 as stored [k][hidden0] (hidden0 even).  form 0 = automatic (what the two calls
+ * above do), 1 = the LDS kernel (8 waves of 32 rows, both operands staged through LDS), 2 = the
+ * register-fed kernel (4 waves of 64 rows, both operands from L2 straight into the MFMA
+ * fragments, no LDS in the K loop, two workgroups per CU); 2 needs k and hidden0 even and
+ * in_features <= 31, else MEPOL_ERR_UNSUPPORTED.  Both kernels use the same tiles, grid,
+ * workspace and records and give the same bits: the register-fed one feeds the LDS kernel's
+ * k-steps to the same lanes and adds a row block's eight 32-row partials in the same order. */
+int mepol_dh1_layer1_backward_form(const double* dz2, int64_t n, int k, const double* W,
+                                   int hidden0, const uint16_t* h1_mask, const double* x,
+                                   int in_features, double* dW1, double* db1, void* workspace,
+                                   size_t workspace_bytes, int w2, int form, void* stream);
+
+/* Host only (no GPU call): which kernel the four calls above launch at these sizes, its grid and
+ * the layout of the workspace.  mask != 0: the bit-mask forms (_masked, _w2, _form); w2 != 0: W2
+ * as stored (needs mask and hidden0 even); ask: the form argument of _form, 0 for the other
+ * calls (ask = 2 where the register-fed kernel does not fit: MEPOL_ERR_UNSUPPORTED).  *form: 1 =
+ * the register-fed kernel, 0 = the LDS kernel.  Automatic choice: the register-fed kernel for a
+ * mask form that fits it and whose grid has more tiles than the chip has CUs (256), the LDS
+ * kernel for everything else, the f64-h1 form included.  *nh = ceil((in_features + 1) / 16); the
+ * grid is *row_blocks x *col_tiles workgroups (256 x 80 tiles) of *threads threads (*
+ * waves_per_block waves of *rows_per_wave rows) and *lds_bytes of LDS; the workspace holds
+ * *row_blocks records of *record_doubles = hidden0 (in_features + 1) doubles, then at byte
+ * *group_offset the 16 group sums of the fixed-order reduction: *ws_bytes in all, as
+ * mepol_dh1_layer1_workspace_size. */
+int mepol_dh1_layer1_plan_info(int64_t n, int k, int hidden0, int in_features, int mask, int w2,
+                               int ask, int* form, int* nh, int* row_blocks, int* col_tiles,
+                               int* threads, int* lds_bytes, int* waves_per_block,
+                               int* rows_per_wave, int64_t* record_doubles, size_t* group_offset,
+                               size_t* ws_bytes);
 
 /* Weight gradient of a linear layer over a tall batch: dW [out, in] = dy^T x with dy [n, out]
  * and x [n, in] row-major f64 (the policy's dW2 = dz2^T h1, K = n), split-K on the f64 matrix

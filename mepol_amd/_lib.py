@@ -68,6 +68,10 @@ SIGNATURES = {
                              _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
                              _c_vp],
     "mepol_dh1_layer1_workspace_size": [_c_i64, _c_int, _c_int, ctypes.POINTER(_c_sz)],
+    "mepol_dh1_layer1_backward_form": [_c_vp, _c_i64, _c_int, _c_vp, _c_int, _c_vp, _c_vp,
+                                       _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_int, _c_int, _c_vp],
+    "mepol_dh1_layer1_plan_info": [_c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + [
+        ctypes.POINTER(_c_int)] * 8 + [ctypes.POINTER(_c_i64)] + [ctypes.POINTER(_c_sz)] * 2,
     "mepol_dh1_layer1_backward": [_c_vp, _c_i64, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_int,
                                   _c_vp, _c_vp, _c_vp, _c_sz, _c_vp],
     "mepol_dh1_layer1_backward_masked": [_c_vp, _c_i64, _c_int, _c_vp, _c_int, _c_vp, _c_vp,

@@ -396,6 +396,272 @@ __global__ __launch_bounds__(l1b::P::kThreads) void dh1_layer1_bwd_kernel(
   }
 }
 
+// ---- the same op with its K loop fed from registers ------------------------------------------
+// The masked dh1 + layer-1 backward in the shape of z2_head_kernel / wgrad_kernel: 4 waves x
+// (64 rows x 80 columns) on the same 256 x 80 tile, xcd_tile order and grid.  Both operands go
+// from L2 straight into the MFMA fragments through mfma::ring_k_loop, no LDS and no barrier in
+// the K loop, two workgroups per CU.
+// The bits are the LDS form's.  Its k-tile of 16 gives lane group g the k-steps 4 g + s, s = 0
+// .. 3; here stage st = 2 kt + hf reads the pair k = 16 kt + 4 g + 2 hf + {0, 1} per lane and
+// fragment, and its two MFMAs are steps s = 2 hf and 2 hf + 1 of that k-tile: the same operands
+// in the same lanes in the same order, all-zero padded steps included.  The epilogue keeps the
+// two 32-row halves of a wave apart and adds the eight half-wave partials in the order of the
+// LDS form's eight waves.
+// BT: W2 as stored, [K][M]: two 8-B loads per fragment and stage (rows k, k + 1; the 16 lanes of
+// a row group read 128 contiguous bytes); else W2^T [M][K], one 16-B load.
+// Operand addresses are 32-bit byte offsets from workgroup-uniform bases (dz2 + row0 K, W2):
+// 9 address registers instead of 18 next to the 160 accumulator registers; direct_fits() bounds
+// the sizes so that they cannot overflow.
+// Epilogue, built to live beside the accumulators:
+//  1. the wave's 64 x 16 NH block of [x | 1] goes once through registers (the ring is dead) into
+//     LDS, already zeroed for rows past N and features past F (a select at the store: a clamped
+//     x value never reaches a sum), 8 values of a lane at a time;
+//  2. dz1 = dh1 . relu'(h1) in place, one row fragment's mask words at a time; a row past N and a
+//     column past M become exact zeros here (their accumulators hold clamped copies, nan where
+//     W2 holds an inf);
+//  3. per column fragment j: NH output fragments per 32-row half, dz1^T [x | 1] with the
+//     accumulator as the A operand and [x | 1] read back from LDS per MFMA; then the partials
+//     summed through LDS in row order into the row block's record, two waves per round.
+// LDS: 40 KB x NH per workgroup, so NH <= 2 keeps two workgroups on a CU.
+namespace l1d {
+constexpr int NW = 4, FO = 4, FI = 5, NS = 2, NL = FO + FI;
+constexpr int BM = NW * 16 * FO, BN = 16 * FI;
+static_assert(BM == l1b::P::BM && BN == l1b::P::BN, "the LDS form's tiles, grid and records");
+constexpr int kThreads = 64 * NW;
+constexpr int kOcc = 2;  // waves per SIMD the register budget is cut for: 256 VGPRs
+// The K loop's issue order is left to the scheduler (mfma_f64.hpp's PIN): pinned, every stage
+// waits vmcnt(23 .. 14) behind its own 14 loads; free, every second stage waits vmcnt(7 .. 1).
+// Both keep 0 scratch; the free order measured 0.4 ms per C3 epoch faster on average and never
+// slower (profiles/r15/dh1_direct/).
+constexpr bool kPin = false;
+constexpr int kMaxNH = 2;  // 3 and 4 need 120 / 160 KB of LDS: one workgroup per CU
+template <int NH>
+constexpr size_t lds_bytes() {
+  return (size_t)NW * (64 * 16 * NH + NH * 4 * 64) * sizeof(double);
+}
+inline size_t lds_bytes(int nh) { return (size_t)nh * lds_bytes<1>(); }
+// the 32-bit operand offsets: (255 K + K) elements of dz2 from the row block's base, K M of W2
+inline bool direct_fits(int k, int m, int F) {
+  const int nh = (F + 1 + 15) / 16;
+  return !(k & 1) && !(m & 1) && nh <= kMaxNH && (int64_t)BM * k < (1 << 28) &&
+         (int64_t)k * m < (1 << 28);
+}
+// Automatic choice: only a grid with more tiles than the chip has CUs.  What this form gains is
+// its second workgroup on a CU (and its place beside wgrad_kernel's waves); a grid that leaves
+// CUs empty gains nothing from that, and measured on such grids it was slower than the LDS form
+// as often as faster (20 to 235 tiles, profiles/r15/dh1_direct/).  The bits do not depend on it.
+constexpr int kCUs = 256;
+inline bool direct_pays(int64_t n, int m) {
+  return (int64_t)l1b::row_blocks(n) * ((m + BN - 1) / BN) > kCUs;
+}
+// form asked for: 0 = automatic, 1 = the LDS kernel, 2 = this one (must fit)
+enum { kAuto = 0, kLds = 1, kDirect = 2 };
+inline bool use_direct(int form, int64_t n, int k, int m, int F) {
+  return form == kDirect || (form == kAuto && direct_fits(k, m, F) && direct_pays(n, m));
+}
+}  // namespace l1d
+
+template <int NH, bool BT>
+__global__ __launch_bounds__(l1d::kThreads) __attribute__((amdgpu_waves_per_eu(l1d::kOcc))) void
+dh1_direct_kernel(const double* __restrict__ dz2, int64_t N, int K, const double* __restrict__ W2,
+                  int M, const uint16_t* __restrict__ hm, const double* __restrict__ x, int F,
+                  double* __restrict__ part) {
+  using namespace l1d;
+  constexpr int NE = NH * 4 * 64, XW = 16 * NH;  // doubles of a wave's partial; of an [x | 1] row
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x, l = tid & 63;
+  int fr = l & 15, g = l >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double* xs = lds + w * 64 * XW;    // [NW][64][XW], 16-value groups swizzled by the row's bit 0
+  double* red = lds + NW * 64 * XW;  // [4][NE]: the half-wave partials of two waves
+  const int ncb = (M + BN - 1) / BN;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
+  // (the division runs on the vector ALU: without readfirstlane rb, row0 and col0 would sit in
+  // vector registers across the K loop)
+  const int rb = __builtin_amdgcn_readfirstlane(tile / ncb);
+  const int64_t row0 = (int64_t)rb * BM, wr0 = row0 + 64 * w;
+  const int col0 = (tile - rb * ncb) * BN;
+  const double* abase = dz2 + row0 * K;  // uniform
+  uint32_t ao[FO], bo[FI];  // byte offsets: base + zero-extended 32 bits is one address mode
+#pragma unroll
+  for (int t = 0; t < FO; ++t)
+    ao[t] = 8u * (uint32_t)((int)(min<int64_t>(wr0 + 16 * t + fr, N - 1) - row0) * K + 4 * g);
+#pragma unroll
+  for (int u = 0; u < FI; ++u) {
+    const int c = min(col0 + 16 * u + fr, M - 1);
+    bo[u] = 8u * (uint32_t)(BT ? 4 * g * M + c : c * K + 4 * g);
+  }
+  const char* ab = reinterpret_cast<const char*>(abase);
+  const char* bb = reinterpret_cast<const char*>(W2);
+  d4 acc[FO][FI];
+#pragma unroll
+  for (int t = 0; t < FO; ++t)
+#pragma unroll
+    for (int u = 0; u < FI; ++u) acc[t][u] = d4{0.0, 0.0, 0.0, 0.0};
+  // stage st reads k = 16 (st / 2) + 4 g + 2 (st % 2) (+1); K is even, so a pair is whole or
+  // past the end.  The address is clamped to the last pair and the pairs past K of the last
+  // k-tile's two stages are zeroed at use (ring_k_loop's tail takes both: nfull is even).
+  const int nst = 2 * ((K + 15) / 16), nfull = 2 * (K / 16);
+  double2 R[NS][NL];
+  auto load = [&](double2 (&D)[NL], int st) __attribute__((always_inline)) {
+    // k + 4 g <= K - 2; a negative k wraps with the offset it is added to, which holds + 4 g
+    const int k = min(16 * (st >> 1) + 2 * (st & 1), K - 2 - 4 * g);
+    const uint32_t ka = 8u * (uint32_t)k, kb = BT ? ka * (uint32_t)M : ka;
+#pragma unroll
+    for (int t = 0; t < FO; ++t) D[t] = *reinterpret_cast<const double2*>(ab + (ao[t] + ka));
+#pragma unroll
+    for (int u = 0; u < FI; ++u) {
+      if constexpr (BT) {
+        D[FO + u].x = *reinterpret_cast<const double*>(bb + (bo[u] + kb));
+        D[FO + u].y = *reinterpret_cast<const double*>(bb + (bo[u] + kb + 8u * (uint32_t)M));
+      } else {
+        D[FO + u] = *reinterpret_cast<const double2*>(bb + (bo[u] + kb));
+      }
+    }
+  };
+  auto mma = [&](const double2 (&D)[NL]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int t = 0; t < FO; ++t)
+#pragma unroll
+      for (int u = 0; u < FI; ++u)
+        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(D[t].x, D[FO + u].x, acc[t][u], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < FO; ++t)
+#pragma unroll
+      for (int u = 0; u < FI; ++u)
+        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(D[t].y, D[FO + u].y, acc[t][u], 0, 0, 0);
+  };
+  mfma::ring_k_loop<NS, kPin>(
+      nfull, nst, [&](int p, int st) __attribute__((always_inline)) { load(R[p], st); },
+      [&](int p, int st) __attribute__((always_inline)) {
+        if (16 * (st >> 1) + 2 * (st & 1) + 4 * g >= K) {  // the last k-tile's missing pairs
+#pragma unroll
+          for (int v = 0; v < NL; ++v) R[p][v] = double2{0.0, 0.0};
+        }
+      },
+      [&](int p) __attribute__((always_inline)) { mma(R[p]); });
+
+  // ---- epilogue: acc[t][u][q] = dh1[row wr0 + 16 t + g + 4 q][col col0 + 16 u + fr] ----------
+  // 1. [x | 1] of the wave's rows into LDS: lane (fr, g) takes feature 16 h + fr of rows 4 it +
+  //    g, which is the B operand of k-step it = 4 i + q (B[k = g][n = fr]).  Group h of a row
+  //    sits at group h ^ (row & 1): the two rows a 32-lane half reads are 16 XW B apart (a
+  //    whole number of 256-B bank rows for even NH), the swizzle puts them on different banks.
+  // (32-bit offsets from the row block's base here too: rows 0 .. nr - 1 of it exist)
+  // The lane index is taken again through an opaque copy: nothing the epilogue needs is then a
+  // value of the prologue's, kept in a register across the K loop (that cost scratch).
+  int le = threadIdx.x;
+  asm volatile("" : "+v"(le));
+  fr = le & 15, g = (le >> 4) & 3;
+  const int nr = (int)min<int64_t>(N - row0, BM);
+  const int wl = 64 * w;  // the wave's first row in the row block
+  const double* xbase = x + row0 * F;
+#pragma unroll
+  for (int h = 0; h < NH; ++h) {
+    const int f = 16 * h + fr;
+#pragma unroll
+    for (int i0 = 0; i0 < 16; i0 += 8) {  // 8 loads in flight, then their 8 stores
+      int xo = 0;
+      asm volatile("" : "+s"(xo));
+      double xv[8];
+#pragma unroll
+      for (int it = 0; it < 8; ++it)
+        xv[it] = xbase[xo + min(wl + 4 * (i0 + it) + g, nr - 1) * F + min(f, F - 1)];
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const bool rin = wl + 4 * (i0 + it) + g < nr;
+        const double v = (rin && f < F) ? xv[it] : ((rin && f == F) ? 1.0 : 0.0);
+        xs[(4 * (i0 + it) + g) * XW + 16 * (h ^ (g & 1 & (NH - 1))) + fr] = v;
+      }
+    }
+  }
+  // 2. dz1 = dh1 * relu'(h1) in place.  Lane (fr, g) loads word min(fr, 4) of the tile's five
+  //    mask words of row 16 i + 4 q + g (16 loads for the whole tile) and takes word j from
+  //    lane j of its row group: one register per row instead of five.
+  const int mw = (M + 15) / 16;
+  const uint16_t* hmb = hm + row0 * mw;
+  const int hc = min((col0 >> 4) + min(fr, FI - 1), mw - 1);
+#pragma unroll
+  for (int i = 0; i < FO; ++i) {
+    uint32_t hv[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) hv[q] = hmb[min(wl + 16 * i + 4 * q + g, nr - 1) * mw + hc];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool rin = wl + 16 * i + 4 * q + g < nr;
+#pragma unroll
+      for (int j = 0; j < FI; ++j) {
+        const uint32_t wj = (uint32_t)__shfl((int)hv[q], 16 * g + j, mepol::kWave);
+        const bool on = rin && col0 + 16 * j + fr < M && ((wj >> fr) & 1u) != 0;
+        acc[i][j][q] = on ? acc[i][j][q] : 0.0;
+      }
+    }
+  }
+  __syncthreads();  // xs is wave-private, but this is the cheapest fence that orders it
+  // 3. per column fragment j: dz1^T [x | 1] on the matrix cores (k-step (i, q): A[m = fr][k =
+  //    g] = dz1 at (row 16 i + 4 q + g, col fr of fragment j), B[k = g][n = fr] = [x | 1] at
+  //    (that row, feature 16 h + fr)), rows 0-31 and 32-63 of the wave into partials of their
+  //    own.  The record is ((((((p0 + p1) + p2) + p3) + p4) + p5) + p6) + p7 over the row
+  //    block's eight 32-row parts: waves 0 and 1 hand over p0 .. p3, then waves 2 and 3 p4 ..
+  //    p7, through the same four LDS slots; thread e keeps the running sums of its NH elements.
+#pragma unroll
+  for (int j = 0; j < FI; ++j) {
+    // [x | 1] is re-read from LDS for every j: an opaque offset (not an opaque pointer, which
+    // would lose the LDS address space) keeps the compiler from holding all 16 NH values of a
+    // lane in registers across the j loop
+    int xo = 0;
+    asm volatile("" : "+s"(xo));
+    const double* xj = xs + xo;
+    d4 dacc[2][NH];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+#pragma unroll
+      for (int h = 0; h < NH; ++h) dacc[hf][h] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int i = 2 * hf; i < 2 * hf + 2; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int h = 0; h < NH; ++h)
+            dacc[hf][h] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                acc[i][j][q],
+                xj[(16 * i + 4 * q + g) * XW + 16 * (h ^ (g & 1 & (NH - 1))) + fr], dacc[hf][h],
+                0, 0, 0);
+    }
+    // dacc[hf][h][r'] = sum over the half's rows of dz1[.][col0 + 16 j + g + 4 r'] *
+    // [x | 1][16 h + fr]
+    double run[NH];
+#pragma unroll
+    for (int rnd = 0; rnd < 2; ++rnd) {
+      if ((w >> 1) == rnd) {  // uniform
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+          for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              red[(2 * (w & 1) + hf) * NE + (h * 4 + q) * 64 + (le & 63)] = dacc[hf][h][q];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int h = 0; h < NH; ++h) {
+        const int e = le + kThreads * h;  // NE = kThreads NH
+        double sum = rnd == 0 ? red[e] : run[h] + red[e];
+#pragma unroll
+        for (int v = 1; v < 4; ++v) sum += red[v * NE + e];
+        run[h] = sum;
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int e = le + kThreads * h;
+      const int ll = e & 63, q = (e >> 6) & 3;  // (e >> 8 is h)
+      const int cc = col0 + j * 16 + (ll >> 4) + 4 * q, f = 16 * h + (ll & 15);
+      if (cc < M && f <= F) part[((int64_t)rb * M + cc) * (F + 1) + f] = run[h];
+    }
+  }
+}
+
 // ---- backward through a hidden layer (GaussianPolicy.net[2 l], l >= 1, src/policy.py:21-26) ---
 // dz_in = (dz_out W) . relu'(h_in) for W [K][M] as stored (gemm_mainloop's BT form) and the
 // layer's ReLU input h_in [N][M], plus the previous layer's bias gradient db_in[c] = sum_r
@@ -608,14 +874,70 @@ extern "C" int mepol_dh1_layer1_workspace_size(int64_t n, int m, int in_features
   return 0;
 }
 
+// Host only (no GPU call): which kernel mepol_dh1_layer1_backward{,_masked,_w2,_form} launches
+// at these sizes (mask: the bit-mask forms; w2: W2 as stored, which implies mask; ask: the form
+// argument of mepol_dh1_layer1_backward_form, 0 for the other three calls), its grid and the
+// layout of the workspace.
+//   form            0 = the LDS kernel (dh1_layer1_bwd_kernel), 1 = the register-fed one
+//   nh              16-column groups of [x | 1]
+//   row_blocks, col_tiles   the grid is their product; tile (rb, ct) = xcd_tile(block)
+//   threads, lds_bytes      of one workgroup
+//   waves_per_block, rows_per_wave   a row block's record is the ordered sum of these waves
+//   record_doubles  hidden0 (in_features + 1): one row block's record
+//   group_offset    byte offset of sum_records' 16 group sums (after the row_blocks records)
+//   ws_bytes        what mepol_dh1_layer1_workspace_size reports
+extern "C" int mepol_dh1_layer1_plan_info(int64_t n, int k, int hidden0, int in_features, int mask,
+                                          int w2, int ask, int* form, int* nh, int* row_blocks,
+                                          int* col_tiles, int* threads, int* lds_bytes,
+                                          int* waves_per_block, int* rows_per_wave,
+                                          int64_t* record_doubles, size_t* group_offset,
+                                          size_t* ws_bytes) {
+  namespace B = mepol::gemm::l1b;
+  namespace D = mepol::gemm::l1d;
+  const int m = hidden0, F = in_features;
+  if (n <= 0 || k <= 0 || (k & 1) || m <= 0 || F <= 0 || F > 63 || (w2 && (!mask || (m & 1))) ||
+      ask < 0 || ask > 2 || !form || !nh || !row_blocks || !col_tiles || !threads || !lds_bytes || !waves_per_block ||
+      !rows_per_wave || !record_doubles || !group_offset || !ws_bytes) {
+    mepol::set_error("mepol_dh1_layer1_plan_info: bad arguments (n, k, hidden0 positive, k even, "
+                     "in_features in 1..63, w2 only with mask and hidden0 even, ask in 0..2; "
+                     "every output non-null)");
+    return mepol::kErrBadArg;
+  }
+  if (ask == D::kDirect && !(mask && D::direct_fits(k, m, F))) {
+    mepol::set_error("mepol_dh1_layer1_plan_info: the register-fed kernel is not available at "
+                     "these sizes (mask forms, k and hidden0 even, in_features <= 31)");
+    return mepol::kErrUnsupported;
+  }
+  const bool direct = mask && D::use_direct(ask, n, k, m, F);
+  *form = direct ? 1 : 0;
+  *nh = (F + 1 + 15) / 16;
+  *row_blocks = B::row_blocks(n);
+  *col_tiles = (m + B::P::BN - 1) / B::P::BN;
+  *threads = direct ? D::kThreads : B::P::kThreads;
+  *lds_bytes = direct ? (int)D::lds_bytes(*nh) : (int)B::P::kLds;
+  *waves_per_block = direct ? D::NW : B::WR;
+  *rows_per_wave = B::P::BM / *waves_per_block;
+  *record_doubles = (int64_t)m * (F + 1);
+  *group_offset = (size_t)*row_blocks * (size_t)*record_doubles * sizeof(double);
+  *ws_bytes = B::ws_bytes(n, m, F);
+  return 0;
+}
+
 template <bool MASK, bool BT = false>
 static int dh1_layer1_backward(const double* dz2, int64_t n, int k, const double* W2t, int m,
                                const void* h1, const double* x, int in_features, double* dW1,
                                double* db1, void* workspace, size_t workspace_bytes,
-                               void* stream) {
+                               void* stream, int form = 0) {
   using namespace mepol::gemm::l1b;
   using mepol::gemm::dh1_layer1_bwd_kernel;
   const int F = in_features;
+  if (form < 0 || form > 2 || (form == 2 && !(MASK && F > 0 && k > 0 && m > 0 &&
+                                              mepol::gemm::l1d::direct_fits(k, m, F)))) {
+    mepol::set_error("mepol_dh1_layer1_backward: form %d is not available at these sizes (0 = "
+                     "automatic, 1 = LDS kernel, 2 = register-fed kernel: k and hidden0 even, "
+                     "in_features <= 31)", form);
+    return form < 0 || form > 2 ? mepol::kErrBadArg : mepol::kErrUnsupported;
+  }
   if (n <= 0 || k <= 0 || (k & 1) || m <= 0 || F <= 0 || F > 63 || !dz2 || !W2t || !h1 || !x ||
       !dW1 || !workspace || ((uintptr_t)dz2 & 15) || ((uintptr_t)W2t & 15) || (BT && (m & 1))) {
     mepol::set_error("mepol_dh1_layer1_backward: bad arguments (k even, in_features <= 63, "
@@ -634,7 +956,34 @@ static int dh1_layer1_backward(const double* dz2, int64_t n, int k, const double
   const unsigned tiles = (unsigned)((int64_t)nrb * ncb);
   double* part = (double*)workspace;
   const int nh = (F + 1 + 15) / 16;
-#define MEPOL_L1B(NHV)                                                                         \
+  // The mask forms take the register-fed kernel where it fits (l1d::direct_fits: K and M even,
+  // NH <= 2) and pays (l1d::direct_pays: more tiles than CUs), or where the caller asks for it.
+  // Its resource report at NH = 1 and 2, both W2 forms: no scratch, no AGPRs, two waves per
+  // SIMD.  NH = 3 and 4 would need 120 and 160 KB of LDS for the [x | 1] block, one workgroup
+  // per CU, and are not instantiated: they, the f64-h1 form and odd sizes keep the LDS kernel.
+  // Both kernels give the same bits.
+  if constexpr (MASK) {
+    if (mepol::gemm::l1d::use_direct(form, n, k, m, F)) {
+      namespace D = mepol::gemm::l1d;
+      using mepol::gemm::dh1_direct_kernel;
+      const uint16_t* hm = static_cast<const uint16_t*>(h1);
+#define MEPOL_L1D(NHV)                                                                         \
+  do {                                                                                         \
+    MEPOL_HIP((mepol::max_dynamic_lds<dh1_direct_kernel<NHV, BT>>((int)D::lds_bytes<NHV>())));  \
+    hipLaunchKernelGGL((dh1_direct_kernel<NHV, BT>), dim3(tiles), dim3(D::kThreads),           \
+                       D::lds_bytes<NHV>(), st, dz2, n, k, W2t, m, hm, x, F, part);            \
+  } while (0)
+      if (nh == 1)
+        MEPOL_L1D(1);
+      else
+        MEPOL_L1D(2);
+#undef MEPOL_L1D
+      MEPOL_CHECK_LAUNCH();
+      return mepol::sum_records<kGroups>(part, nrb, (int64_t)m * (F + 1), ScatterW1{F, dW1, db1},
+                                         st);
+    }
+  }
+#define MEPOL_L1B(NHV)                                                                        \
   do {                                                                                         \
     MEPOL_HIP((mepol::max_dynamic_lds<dh1_layer1_bwd_kernel<NHV, MASK, BT>>((int)P::kLds)));   \
     hipLaunchKernelGGL((dh1_layer1_bwd_kernel<NHV, MASK, BT>), dim3(tiles), dim3(P::kThreads),  \
@@ -677,6 +1026,22 @@ extern "C" int mepol_dh1_layer1_backward_w2(const double* dz2, int64_t n, int k,
                                             void* stream) {
   return dh1_layer1_backward<true, true>(dz2, n, k, W2, m, h1_mask, x, in_features, dW1, db1,
                                          workspace, workspace_bytes, stream);
+}
+
+// The two mask forms (w2 == 0: W = W2^T [hidden0][k]; w2 != 0: W = W2 as stored) with the kernel
+// chosen by the caller: form 0 = automatic (what the two calls above do), 1 = the LDS kernel,
+// 2 = the register-fed kernel (MEPOL_ERR_UNSUPPORTED where it does not fit).  The same bits
+// whichever runs.
+extern "C" int mepol_dh1_layer1_backward_form(const double* dz2, int64_t n, int k, const double* W,
+                                              int m, const uint16_t* h1_mask, const double* x,
+                                              int in_features, double* dW1, double* db1,
+                                              void* workspace, size_t workspace_bytes, int w2,
+                                              int form, void* stream) {
+  if (w2)
+    return dh1_layer1_backward<true, true>(dz2, n, k, W, m, h1_mask, x, in_features, dW1, db1,
+                                           workspace, workspace_bytes, stream, form);
+  return dh1_layer1_backward<true>(dz2, n, k, W, m, h1_mask, x, in_features, dW1, db1, workspace,
+                                   workspace_bytes, stream, form);
 }
 
 

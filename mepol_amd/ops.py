@@ -440,11 +440,12 @@ def dh1_layer1_ok(in_features, hidden1):
 
 
 def dh1_layer1_backward(dz2, W2t, h1, x, ws=None, dW_out=None, db_out=None, mask=None,
-                        w2=None):
+                        w2=None, form="auto"):
     """(dW1, db1) of h1 = relu(x W1^T + b1) from dz2 = dL/dz2 [n, h1w] and W2t = W2^T
     [h0, h1w]: dh1 = dz2 W2 is reduced on chip (csrc/gemm.hip), never written.  With `w2`
     (W2 as stored, [h1w, h0]; needs `mask`) W2t is not read and may be None: the kernel
-    transposes W2's tiles itself (mepol_dh1_layer1_backward_w2)."""
+    transposes W2's tiles itself (mepol_dh1_layer1_backward_w2).  form (mask forms only): "auto",
+    or "lds" / "direct" to name the kernel (dh1_layer1_plan; the same bits either way)."""
     n, k = dz2.shape
     f = x.shape[1]
     if w2 is not None:
@@ -458,7 +459,13 @@ def dh1_layer1_backward(dz2, W2t, h1, x, ws=None, dW_out=None, db_out=None, mask
                                                       device=x.device)
     db = db_out if db_out is not None else torch.empty(h0, dtype=torch.float64, device=x.device)
     assert dW.is_contiguous() and db.is_contiguous()
-    if w2 is not None:
+    if form != "auto":
+        assert mask is not None and mask.shape == (n, (h0 + 15) // 16)
+        assert mask.dtype == torch.int16
+        call("mepol_dh1_layer1_backward_form", ptr(dz2), n, k, ptr(w2 if w2 is not None else W2t),
+             h0, ptr(mask), ptr(x), f, ptr(dW), ptr(db), ptr(ws), ws.numel(),
+             int(w2 is not None), DH1_FORMS[form], _stream())
+    elif w2 is not None:
         assert mask.shape == (n, (h0 + 15) // 16) and mask.dtype == torch.int16
         call("mepol_dh1_layer1_backward_w2", ptr(dz2), n, k, ptr(w2), h0, ptr(mask), ptr(x), f,
              ptr(dW), ptr(db), ptr(ws), ws.numel(), _stream())
@@ -470,6 +477,29 @@ def dh1_layer1_backward(dz2, W2t, h1, x, ws=None, dW_out=None, db_out=None, mask
         call("mepol_dh1_layer1_backward_masked", ptr(dz2), n, k, ptr(W2t), h0, ptr(mask),
              ptr(x), f, ptr(dW), ptr(db), ptr(ws), ws.numel(), _stream())
     return dW, db
+
+
+DH1_FORMS = {"auto": 0, "lds": 1, "direct": 2}
+
+
+def dh1_layer1_plan(n, k, hidden0, in_features, mask=True, w2=False, form="auto"):
+    """Which kernel dh1_layer1_backward launches at these sizes (host only:
+    mepol_dh1_layer1_plan_info): {"form": "direct" (operands from L2 into registers) or "lds",
+    "nh", "row_blocks", "col_tiles", "threads", "lds_bytes", "waves_per_block", "rows_per_wave",
+    "record_doubles", "group_offset", "ws_bytes"}.  mask: the bit-mask forms; w2: W2 as stored;
+    form: as asked of dh1_layer1_backward."""
+    names = ("form", "nh", "row_blocks", "col_tiles", "threads", "lds_bytes", "waves_per_block",
+             "rows_per_wave")
+    ints = {k_: ctypes.c_int() for k_ in names}
+    rec = ctypes.c_int64()
+    off, wsb = ctypes.c_size_t(), ctypes.c_size_t()
+    call("mepol_dh1_layer1_plan_info", n, k, hidden0, in_features, int(bool(mask)), int(bool(w2)),
+         DH1_FORMS[form], *[ctypes.byref(ints[k_]) for k_ in names], ctypes.byref(rec), ctypes.byref(off),
+         ctypes.byref(wsb))
+    plan = {k_: v.value for k_, v in ints.items()}
+    plan["form"] = "direct" if plan["form"] == 1 else "lds"
+    plan.update(record_doubles=rec.value, group_offset=off.value, ws_bytes=wsb.value)
+    return plan
 
 
 def weight_grad_workspace(n, out_features, in_features, device):

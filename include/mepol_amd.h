@@ -59,9 +59,15 @@ int mepol_memcpy_async(void* dst, const void* src, size_t bytes, void* stream);
  * split_hint: 0 = automatic candidate split.  Any d >= 1 and any 1 <= kp1 <= n_cand (sklearn
  * raises for kp1 > n_samples; so does this, MEPOL_ERR_BAD_ARG); n_cand < 2^31 - 64.  Plans:
  * d <= 63 and kp1 <= 60 run the f16 MFMA screen + certified f64 re-rank (queries it cannot
- * certify take the exhaustive scan); every other shape, and any input with a row whose f32
- * squared norm overflows (the screen cannot scale it), is answered by the exhaustive f64 scan
- * for every query (mepol_knn_plan_info reports *ks = 0 for such a plan).
+ * certify take the exhaustive scan); every other shape is answered by the exhaustive f64 scan
+ * for every query (mepol_knn_plan_info reports *ks = 0 for such a plan).  The screen's
+ * certification bound e 2^-24 (C^2 + 2 C |q|), C = max candidate norm, is relative; it holds for
+ * 2^-56 <= max(C, Q) < 2^62 and Q <= 2^8 C, Q = max query norm (the self k-NN and a query shard
+ * of the candidates have Q <= C).  Any other input -- a row whose f32 squared norm overflows,
+ * norms so small or large that the screen's f32 scale or its values leave f32, queries more than
+ * 2^5 times larger than every candidate (the test keeps 2^3 for the norms' own error) -- is
+ * valid: the screen is skipped and every query takes the exhaustive f64 scan, with
+ * *n_fallback_out = n_query.
  * Input validation (sklearn's check_array in fit/kneighbors): a NaN / inf coordinate in cand or
  * query returns MEPOL_ERR_BAD_ARG ("Input contains NaN or infinity").  The check synchronises
  * `stream` once per call (before the scan is launched), as the reference's kneighbors call

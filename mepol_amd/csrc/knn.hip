@@ -22,7 +22,10 @@
 //                bitonic-sort by (dist, idx), and certify with a rigorous bound on the f16
 //                selection's error that no excluded candidate can enter the top-(k+1).
 //                Uncertified queries (near-ties across the boundary, duplicate clusters) are
-//                queued.
+//                queued.  The bound is relative: it holds for 2^-56 <= max norm < 2^62 and
+//                max |q| <= 2^8 max |c| (off_screen_domain, knn_common.hpp, has the derivation);
+//                for any other input steps 1 to 3 return at once and step 4 answers every
+//                query, as for a squared norm that overflows f32.
 //   4. exact   : queued queries are answered by an exhaustive f64 scan (no approximation),
 //                a handful of queries spread over the whole grid (chunked scan + merge).
 #include "knn_common.hpp"
@@ -36,7 +39,14 @@ namespace knn {
 // max |x| over candidates (scal[0]) and over queries (scal[2]), non-negative float bit order.
 // Input validation (sklearn's check_array inside NearestNeighbors.fit / kneighbors,
 // mepol.py:190-192): rows with a NaN / inf coordinate are counted in bad[0], rows whose f32
-// squared norm overflows (|x| >~ 1.8e19) in bad[1].  The tests are on laundered bit patterns: this
+// squared norm overflows (|x| >~ 1.8e19) in bad[1].  A row with a nonzero coordinate whose f32
+// squared norm falls below the normal range (|x| <~ 1.1e-19: it carries few bits, or none) is
+// reported by its largest |coordinate| with 3 added to the exponent field instead: at least
+// |x| for d <= 63 (and at most 8 |x| unless the coordinate is itself subnormal).  Such data
+// must not look all-zero, and it is below the screen's domain anyway unless larger rows set the
+// maxima (off_screen_domain, knn_common.hpp).  The maxima are taken on the bit patterns (the
+// order of non-negative floats), subnormal values included.  The tests are on laundered bit
+// patterns: this
 // TU is built with -fno-honor-nans (for the selection kernels), under which the compiler rewrites
 // a plain exponent test into |x| == inf and loses NaN.  Once validated, no NaN reaches the
 // selection / refine / exact kernels, so the flag cannot change their results.
@@ -85,10 +95,10 @@ __global__ __launch_bounds__(kNormsThreads) void norms_kernel(const float* __res
                                                            unsigned* __restrict__ bad,
                                                            unsigned* __restrict__ out_bits2) {
   extern __shared__ float sx[];
-  __shared__ float s_nrm[kNormsThreads / 64];
+  __shared__ unsigned s_nrm[kNormsThreads / 64];
   __shared__ unsigned s_bad[2];
   if (threadIdx.x == 0) s_bad[0] = s_bad[1] = 0u;
-  float nrm = 0.f;
+  unsigned nrm = 0;  // bit pattern of the largest row norm
   unsigned nonfinite_rows = 0, overflow_rows = 0;
   for (int64_t r0 = (int64_t)blockIdx.x * kStageRows; r0 < n; r0 += (int64_t)gridDim.x * kStageRows) {
     __syncthreads();  // the previous step's LDS reads are done
@@ -106,11 +116,14 @@ __global__ __launch_bounds__(kNormsThreads) void norms_kernel(const float* __res
       const bool overflow = !nonfinite && nonfinite_bits(s2);
       nonfinite_rows += nonfinite;
       overflow_rows += overflow;
-      if (!nonfinite && !overflow) nrm = fmaxf(nrm, sqrtf(s2));
+      if (!nonfinite && !overflow) {
+        const bool tiny = mag != 0u && (__float_as_uint(s2) & 0x7f800000u) == 0u;
+        nrm = max(nrm, tiny ? mag + (3u << 23) : __float_as_uint(sqrtf(s2)));
+      }
     }
   }
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) nrm = fmaxf(nrm, __shfl_xor(nrm, m, kWave));
+  for (int m = 32; m >= 1; m >>= 1) nrm = max(nrm, (unsigned)__shfl_xor((int)nrm, m, kWave));
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) s_nrm[w] = nrm;
   __syncthreads();
@@ -118,23 +131,13 @@ __global__ __launch_bounds__(kNormsThreads) void norms_kernel(const float* __res
   if (overflow_rows) atomicAdd(&s_bad[1], overflow_rows);
   __syncthreads();
   if (threadIdx.x == 0) {
-    float m = s_nrm[0];
-    for (int i = 1; i < kNormsThreads / 64; ++i) m = fmaxf(m, s_nrm[i]);
-    atomicMax(out_bits, __float_as_uint(m));
-    if (out_bits2) atomicMax(out_bits2, __float_as_uint(m));
+    unsigned m = s_nrm[0];
+    for (int i = 1; i < kNormsThreads / 64; ++i) m = max(m, s_nrm[i]);
+    atomicMax(out_bits, m);
+    if (out_bits2) atomicMax(out_bits2, m);
     if (s_bad[0]) atomicAdd(bad, s_bad[0]);
     if (s_bad[1]) atomicAdd(bad + 1, s_bad[1]);
   }
-}
-
-// The f16 screen does not run for this input: norms_kernel counted into scal[4] the rows with a
-// NaN / inf coordinate (rejected input: the deferred entry point does not stop the stream to
-// look, so every later kernel returns at once, the outputs are undefined and the caller raises)
-// and into scal[5] the finite rows whose squared norm overflows f32 (valid input that the f16
-// scale cannot represent: the screen is skipped and every query takes the exhaustive f64 stage,
-// knn_exact.hip).  Only scal[4] is a rejection.
-__device__ __forceinline__ bool skip_screen(const unsigned* __restrict__ scal) {
-  return (scal[4] | scal[5]) != 0u;
 }
 
 // apack16[((t*64 + l)*KS16 + s)*16 + {0..7 hi, 8..15 lo}] = A[i = l&31][k = 16 s + 8 (l>>5) + j]
@@ -502,7 +505,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void r
   const double ek = __shfl(dd, kp1 - 1, kWave);
   const int eki = __shfl(di, kp1 - 1, kWave);
   bool ok = eki != INT_MAX;
-  if (bnd < 1e29f) ok = ok && (ek < ((double)bnd + qn2) - E);
+  // bnd = +inf: the lists hold every candidate (nothing was excluded)
+  if (bnd < INFINITY) ok = ok && (ek < ((double)bnd + qn2) - E);
   if (l < kp1) {
     Dout[q * kp1 + l] = sqrt_rn(dd);
     if (I64) I64[q * kp1 + l] = di;
@@ -617,6 +621,10 @@ static int make_plan(int64_t nc, int64_t nq, int d, int kp1, int split_hint, Pla
   // output summed in f32 (<= 2K roundings) and |c|^2 in f32 (d roundings), these small terms
   // x2, and 64 for the f16 subnormal range.  Split candidates: 3 K products summed in f32,
   // operand splitting 3 * 2^-22 = 12 * 2^-24, |c|^2 in f32 (d), x2.
+  // Every term is relative.  The absolute ones -- f16's 2^-25 floor below 2^-14 in scaled units,
+  // which the 64 (the doubling, for split candidates) pays for while sigma C >= 1/4, and the f32
+  // range of sigma^2 and of the reported values -- bound the domain: off_screen_domain
+  // (knn_common.hpp); outside it the screen does not run.
   P->e_terms = P->nh == 1 ? 8192 + 64 + 2 * (2 * 16 * P->KS16 + 16 + d)
                           : 2 * (3 * 16 * P->KS16 + 16 + d);
   // Candidate-hi plans with <= 3 k-steps (d <= 47) drop the query's lo half too
@@ -876,7 +884,7 @@ static int knn_impl(const float* cand, int64_t n_cand, const float* query, int64
   launch_refine(P, cpad, query, lv, li, cmax, dist_out, idx_out, idx32_out, fcount, flist, fbound,
                 st);
   MEPOL_CHECK_LAUNCH();
-  // 4. queued queries (or all of them, scal[5]) by the exhaustive stage
+  // 4. queued queries (or all of them: screen_unscalable) by the exhaustive stage
   ea.flag_list = flist;
   ea.flag_bound = fbound;
   ea.part_d = (double*)(ws + P.off_part);

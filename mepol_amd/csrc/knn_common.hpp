@@ -58,7 +58,8 @@ __device__ __forceinline__ unsigned lds_addr(T* p) {
 // Row (candidate within the tile) of accumulator register r for lane l (32x32 C/D map).
 __device__ __forceinline__ int acc_row(int r, int l) { return (r & 3) + 8 * (r >> 2) + 4 * (l >> 5); }
 
-// sigma = 2^e with sigma * max(cmax, qmax) in (64, 128] (1 when the data is all zero).
+// sigma = 2^e with sigma * max(cmax, qmax) in (64, 128] (1 when the data is all zero).  The clamp
+// of e is never reached inside the screen's domain (off_screen_domain: |e| <= 63).
 __device__ __forceinline__ float knn_scale(const unsigned* __restrict__ scal) {
   const float m = fmaxf(__uint_as_float(scal[0]), __uint_as_float(scal[2]));
   // slack for the f32 rounding of sqrt in norms_kernel: 127.9 instead of 128
@@ -67,6 +68,53 @@ __device__ __forceinline__ float knn_scale(const unsigned* __restrict__ scal) {
   (void)frexpf(127.9f / m, &e);
   e = max(-100, min(100, e - 1));
   return ldexpf(1.f, e);
+}
+
+// ---------------------------------------------------------------------------------------
+// The domain of the f16 screen
+// ---------------------------------------------------------------------------------------
+// refine's certification bound E = e_terms 2^-24 (C^2 + 2 C |q|) (make_plan) is purely relative.
+// It holds while, with m = max(C, Q) the larger of the two maximum norms (scal[0], scal[2]):
+//   * 2^-56 <= m < 2^62.  sigma = 2^e has sigma m in (64, 128], the selection reports its values
+//     times 1 / sigma^2 in f32 and they are at most 3 (sigma m)^2 < 2^16 in scaled units: below
+//     2^-56, sigma^2 >= 2^128 overflows (every reported value and bound becomes 0); from 2^62 on
+//     2^16 / sigma^2 can (values and bounds become +inf).  Squared norms that leave f32 altogether
+//     (norms_kernel: scal[5], and the rows it reports by their largest coordinate) lie beyond.
+//   * Q <= 2^8 C.  f16 also has an absolute floor: an operand below 2^-14 in scaled units is
+//     rounded to a multiple of 2^-24, error <= 2^-25 whatever its size, and so is the lo half of
+//     every operand.  Over the K products of A = [-2 sigma c, |sigma c|^2], B = [sigma q, 1] that is
+//     at most 2^-25 (sqrt(d) sigma |q| + 2 sqrt(d) sigma |c| + 1) in scaled units.  The bound keeps
+//     64 2^-24 ((sigma C)^2 + 2 sigma C sigma |q|) for it (the "+ 64" of candidate-hi plans, the
+//     doubled small terms, >= 65, of split-candidate plans), which covers the three terms once
+//     256 sigma C >= sqrt(d), 64 sigma C >= 16 and 64 (sigma C)^2 >= 1 (d <= 63): sigma C >= 1/4,
+//     that is C >= m / 2^8.  With Q <= C (the self k-NN of the epoch, a query shard of the
+//     candidates) sigma C > 64.  Large candidates against small queries need nothing: the
+//     (sigma C)^2 term carries the floor.  The test is Q <= 2^5 C: norms_kernel reports a row
+//     whose squared norm underflows up to 2^3 too large.
+// Outside this domain the screen does not run and every query takes the exhaustive f64 stage,
+// as for scal[5].  All-zero input (m == 0) stays: nothing certifies there (E = 1e-300 against
+// ties at 0).  Integer tests on the bit patterns of the non-negative norms: no dependence on how
+// f32 subnormals compare.
+constexpr unsigned kScreenMinBits = 0x23800000u;  // 2^-56
+constexpr unsigned kScreenMaxBits = 0x5e800000u;  // 2^62
+constexpr unsigned kScreenQcBits = 5u << 23;      // exponent field: x 2^5
+__device__ __forceinline__ bool off_screen_domain(const unsigned* __restrict__ scal) {
+  const unsigned c = scal[0], q = scal[2], m = max(c, q);
+  return m != 0u && (m < kScreenMinBits || m >= kScreenMaxBits || q > c + kScreenQcBits);
+}
+
+// The f16 screen does not run for this input: norms_kernel counted into scal[4] the rows with a
+// NaN / inf coordinate (rejected input: the deferred entry point does not stop the stream to
+// look, so every later kernel returns at once, the outputs are undefined and the caller raises)
+// and into scal[5] the finite rows whose squared norm overflows f32, or the norms are outside
+// the screen's domain (above).  The last two are valid input that the f16 scale cannot
+// represent: the screen is skipped and every query takes the exhaustive f64 stage
+// (knn_exact.hip).  Only scal[4] is a rejection.
+__device__ __forceinline__ bool screen_unscalable(const unsigned* __restrict__ scal) {
+  return scal[5] != 0u || off_screen_domain(scal);
+}
+__device__ __forceinline__ bool skip_screen(const unsigned* __restrict__ scal) {
+  return scal[4] != 0u || screen_unscalable(scal);
 }
 
 __device__ __forceinline__ void split_f16(float v, _Float16& hi, _Float16& lo) {
@@ -169,7 +217,8 @@ __device__ __forceinline__ double sqrt_rn(double x) {
 // ---------------------------------------------------------------------------------------
 // Which queries the stage answers: the queue refine filled (flag_count / flag_list), or every
 // query -- a plan that screens nothing (exhaustive plans) or an input the f16 screen cannot
-// scale (a squared norm beyond f32: scal[5] != 0; the f64 scan has no such limit).  Nothing
+// scale (screen_unscalable: a squared norm beyond f32, scal[5] != 0, or norms outside the
+// screen's domain; the f64 scan has no such limit).  Nothing
 // at all when the input was rejected (scal[4]: a NaN / inf coordinate).
 struct ExactArgs {
   const float* cand;      // [nc][d] row-major (the caller's input)
@@ -181,7 +230,7 @@ struct ExactArgs {
   int kp1;
   int* flag_count;        // queued queries (refine); set to nq when scal[5] sends all
   const int* flag_list;
-  const unsigned* scal;   // [4]: rejected rows, [5]: rows beyond the f16 screen
+  const unsigned* scal;   // [0], [2]: max norms, [4]: rejected rows, [5]: rows beyond the screen
   int all;                // 1: every query (exhaustive plan)
   double* D;
   int64_t* I64;

@@ -22,15 +22,16 @@ namespace knn {
 // Queries of the stage (ExactArgs): returns the count, 0 for a rejected input.
 __device__ __forceinline__ int stage_count(const ExactArgs& a) {
   if (a.scal && a.scal[4]) return 0;
-  return (a.all || (a.scal && a.scal[5])) ? (int)a.nq : *a.flag_count;
+  return (a.all || (a.scal && screen_unscalable(a.scal))) ? (int)a.nq : *a.flag_count;
 }
 __device__ __forceinline__ int64_t stage_query(const ExactArgs& a, int fi) {
-  return (a.all || (a.scal && a.scal[5])) ? (int64_t)fi : (int64_t)a.flag_list[fi];
+  return (a.all || (a.scal && screen_unscalable(a.scal))) ? (int64_t)fi : (int64_t)a.flag_list[fi];
 }
 // A screened plan whose input the screen could not scale reports every query as answered by
 // this stage (the count the caller reads as n_fallback).  One thread of the stage's first kernel.
 __device__ __forceinline__ void stage_report(const ExactArgs& a) {
-  if (blockIdx.x == 0 && threadIdx.x == 0 && !a.all && a.scal && !a.scal[4] && a.scal[5])
+  if (blockIdx.x == 0 && threadIdx.x == 0 && !a.all && a.scal && !a.scal[4] &&
+      screen_unscalable(a.scal))
     *a.flag_count = (int)a.nq;
 }
 
@@ -130,7 +131,7 @@ __host__ __device__ inline int exact_nchunk(int count, int grid) {
 // (C2S, ~600-1300 queued queries on dense d = 2 data: the per-thread list insertions were the
 // stage's cost).  The relative slack only admits more candidates; the answer is the same.
 __device__ __forceinline__ double stage_bound(const ExactArgs& a, int fi) {
-  if (!a.flag_bound || a.all || (a.scal && a.scal[5])) return INFINITY;
+  if (!a.flag_bound || a.all || (a.scal && screen_unscalable(a.scal))) return INFINITY;
   const double b = a.flag_bound[fi];
   return b * (1.0 + 0x1p-40);
 }

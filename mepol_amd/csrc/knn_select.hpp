@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC))) void
   const bool xcd_map = (split & 7) == 0;
   const int sp = xcd_map ? (int)(lin % split) : (int)blockIdx.y;
   const int64_t qt0 = (xcd_map ? lin / split : (int64_t)blockIdx.x) * 4 + w;
-  if (qt0 * 32 >= nq || (scal[4] | scal[5])) return;  // wave-uniform (rejected input: knn.hip)
+  if (qt0 * 32 >= nq || skip_screen(scal)) return;  // wave-uniform (rejected input: knn.hip)
   const int h = l >> 5;
   const float sg = knn_scale(scal);
   const float inv_s2 = 1.f / (sg * sg);  // exact: sigma is a power of two
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void probe16_kernel(const _Float16* __restrict
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int l = threadIdx.x & 63;
   const int64_t qt0 = (int64_t)blockIdx.x * 4 + w;
-  if (qt0 * 32 >= nq || (scal[4] | scal[5])) return;  // wave-uniform
+  if (qt0 * 32 >= nq || skip_screen(scal)) return;  // wave-uniform
   const int h = l >> 5;
   const float sg = knn_scale(scal);
   constexpr bool kQueryLo = NH == 2 || KS16 >= 4;

@@ -26,6 +26,9 @@ FLAGS_knn_select_ks1 := $(FLAGS_knn)
 FLAGS_knn_select_ks2 := $(FLAGS_knn)
 FLAGS_knn_select_ks3 := $(FLAGS_knn)
 FLAGS_knn_select_ks4 := $(FLAGS_knn)
+# the critic fit's accumulators feed its VALU epilogues and Adam: MFMA results in VGPRs (no
+# accvgpr copies around every k-step)
+FLAGS_critic_fit := -mllvm -amdgpu-mfma-vgpr-form
 
 $(LIB): $(OBJ)
 	$(HIPCC) $(FLAGS) -shared -o $@ $(OBJ)

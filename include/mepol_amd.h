@@ -34,7 +34,9 @@ extern "C" {
 
 /* Bumped on every incompatible change of the signatures below (2: mepol_rollout_mlp takes a
  * workspace; mepol_gemm_dpp removed; 3: mepol_iw_normalize_gathered takes the per-rank
- * trajectory sums).  mepol_abi_version() returns the library's value. */
+ * trajectory sums).  Additions keep the number: the *_plan_info queries, and mepol_critic_fit
+ * with mepol_critic_fit_plan_info, came in at 4.  mepol_abi_version() returns the library's
+ * value. */
 #define MEPOL_ABI_VERSION 4
 
 #define MEPOL_ERR_BAD_ARG 1001
@@ -532,6 +534,30 @@ int mepol_optim_step_snapshot(int kind, int n_tensors, double* const* params,
                               const double* scalars, double* const* params_snap,
                               double* const* exp_avg_snap, double* const* exp_avg_sq_snap,
                               void* stream);
+
+/* ---- TRPO's critic fit (src/algorithms/trpo.py:441-457) -----------------------------------------
+ * Replaces the Adam branch's DataLoader loop
+ *     for mb_states, mb_targets in dloader:
+ *         loss = mean((vfunc(mb_states) - mb_targets) ** 2); loss.backward(); optimizer.step()
+ * by ONE launch of one resident workgroup that takes n_steps Adam steps of the critic
+ * Linear(nf, h0) -> ReLU -> Linear(h0, h1) -> ReLU -> Linear(h1, 1), f64, with no L2 term.
+ * states [n, nf], targets [n]; index [n_steps * batch] int32: step s fits rows
+ * index[s * batch .. (s + 1) * batch) (the caller's shuffle; no random numbers are drawn here; an
+ * index outside [0, n) reads nothing and turns that step's results into NaN).  params / exp_avg /
+ * exp_avg_sq: six device pointers each, in torch's order (W1 [h0, nf], b1, W2 [h1, h0], b2,
+ * W3 [1, h1], b3), updated in place; they stay on chip between steps.  scal [n_steps][2] is DEVICE
+ * memory: {lr / bias_correction1, sqrt(bias_correction2)} of each step, the host-computed scalars
+ * of mepol_optim_step.  loss_out [n_steps] (nullable): each step's mini-batch loss before its
+ * update.  Every sum has a fixed order: the same inputs give the same bits.
+ * 1 <= nf <= 16, 1 <= h0, h1 <= 64, 1 <= batch <= 64, n_steps >= 1, n < 2^31 (beyond:
+ * MEPOL_ERR_BAD_ARG).  mepol_critic_fit_plan_info (host only, always 0): the workgroup's threads,
+ * its LDS bytes, and *accepted = 1 when the shape is within those limits, else 0. */
+int mepol_critic_fit_plan_info(int nf, int h0, int h1, int batch, int* threads, int* lds_bytes,
+                               int* accepted);
+int mepol_critic_fit(const double* states, const double* targets, int64_t n, const int32_t* index,
+                     int64_t n_steps, int batch, int nf, int h0, int h1, double* const* params,
+                     double* const* exp_avg, double* const* exp_avg_sq, const double* scal,
+                     double beta1, double beta2, double eps, double* loss_out, void* stream);
 
 #ifdef __cplusplus
 }

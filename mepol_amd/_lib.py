@@ -130,6 +130,9 @@ SIGNATURES = {
     "mepol_optim_step": [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],
     "mepol_optim_step_snapshot": [_c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                   _c_vp, _c_vp, _c_vp, _c_vp],
+    "mepol_critic_fit_plan_info": [_c_int, _c_int, _c_int, _c_int] + [ctypes.POINTER(_c_int)] * 3,
+    "mepol_critic_fit": [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_int,
+                         _c_vp, _c_vp, _c_vp, _c_vp, _c_dbl, _c_dbl, _c_dbl, _c_vp, _c_vp],
 }
 _RESTYPES = {"mepol_last_error_string": ctypes.c_char_p}
 

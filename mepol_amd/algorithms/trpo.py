@@ -31,8 +31,13 @@ launch each (ops.rollout_goal: termination and the sparse reward inside the kern
 reference's step budget on the device (ops.traj_budget) and reads two words per round;
 process_batch computes targets, GAE advantages and the packed batch with ops.gae and
 ops.standardize.  Every other env, policy or device takes the reference's sequential loop, and
-CPU tensors a numpy restatement of the same arithmetic.  The critic stays a torch module under
-autograd.
+CPU tensors a numpy restatement of the same arithmetic.
+
+Critic fit ("Critic fit").  The critic is a torch module; the Adam branch of its fit
+(all critic_iters passes over the DataLoader's mini-batches) runs as one launch of one resident
+workgroup (ops.critic_fit) where kernel_path.critic_fit_ok accepts the critic and its optimizer,
+over the same mini-batches and with the optimizer's state left as the loop would leave it.
+L-BFGS, CPU critics and other shapes take the reference's loop under autograd.
 
 conj_gradient, assign_flat_params and backtracking keep the reference's names, argument order
 and control flow.
@@ -556,9 +561,81 @@ def process_batch(states, actions, rewards, real_traj_lens, dones, values, gamma
 # ---------------------------------------------------------------------------------------------
 # Driver (trpo.py:204-493)
 # ---------------------------------------------------------------------------------------------
+CRITIC_FIT_STATS = {"path": None, "kernel_calls": 0, "steps": 0}
+
+
+def critic_fit_index(n, critic_iters, critic_batch_size):
+    """Row indices of the mini-batches DataLoader(TensorDataset(...), batch_size, shuffle=True,
+    drop_last=True) yields over critic_iters passes, [critic_iters * (n // batch) * batch] int32
+    on the host, with the same draws from torch's global CPU generator: per pass the iterator's
+    base seed, then the RandomSampler's own seed and permutation."""
+    keep = (n // critic_batch_size) * critic_batch_size
+    sampler = torch.utils.data.RandomSampler(range(n))
+    passes = []
+    for _ in range(critic_iters):
+        torch.empty((), dtype=torch.int64).random_()  # the DataLoader iterator's base seed
+        passes.append(torch.tensor(list(sampler), dtype=torch.int32)[:keep])
+    return torch.cat(passes)
+
+
+def _fit_critic_kernel(params, vfunc_optimizer, epoch_states, epoch_targets, critic_iters,
+                       critic_batch_size):
+    """All critic_iters passes of the Adam fit in one launch (ops.critic_fit), leaving
+    vfunc_optimizer's state as its own steps would: moments in place, step advanced."""
+    index = critic_fit_index(epoch_states.shape[0], critic_iters, critic_batch_size)
+    n_steps = index.numel() // critic_batch_size
+    state = vfunc_optimizer.state
+    for p in params:  # a fresh optimizer: the entries Adam itself creates at its first step
+        if len(state[p]) == 0:
+            state[p]["step"] = torch.tensor(0.0, dtype=_scalar_dtype())
+            state[p]["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state[p]["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+    g = vfunc_optimizer.param_groups[0]
+    first = int(float(state[params[0]]["step"])) + 1
+    with torch.no_grad():
+        ops.critic_fit(epoch_states, epoch_targets.reshape(-1), index.to(epoch_states.device),
+                       critic_batch_size, [p.data for p in params],
+                       [state[p]["exp_avg"] for p in params],
+                       [state[p]["exp_avg_sq"] for p in params], g["lr"], betas=g["betas"],
+                       eps=g["eps"], first_step=first)
+    for p in params:
+        state[p]["step"] += n_steps
+        p.grad = None
+    CRITIC_FIT_STATS["kernel_calls"] += 1
+    CRITIC_FIT_STATS["steps"] += n_steps
+
+
+def _scalar_dtype():
+    try:
+        from torch.optim.optimizer import _get_scalar_dtype
+
+        return _get_scalar_dtype()
+    except ImportError:
+        return torch.float32
+
+
 def _fit_critic(vfunc, vfunc_optimizer, optimizer, epoch_states, epoch_targets, critic_reg,
                 critic_iters, critic_batch_size):
-    """The reference's critic update (trpo.py:426-457)."""
+    """The reference's critic update (trpo.py:426-457).  Its Adam branch runs as one launch
+    (ops.critic_fit) over the mini-batches the DataLoader would have drawn when
+    kernel_path.critic_fit_ok accepts the critic and its optimizer; else, and for L-BFGS, the
+    reference's loop.  CRITIC_FIT_STATS['path'] names the path taken."""
+    params = None
+    if optimizer != 'lbfgs' and critic_iters >= 1:
+        # targets [N, 1], as process_batch returns them: against the critic's [B, 1] output a
+        # 1-D target broadcasts to [B, B] in the loop below, which is another loss
+        tgt = epoch_targets
+        if (tgt.dim() == 2 and tgt.shape[1] == 1 and tgt.is_cuda and tgt.dtype == torch.float64
+                and tgt.is_contiguous() and epoch_states.dim() == 2
+                and epoch_states.is_contiguous() and tgt.shape[0] == epoch_states.shape[0]):
+            params = kernel_path.critic_fit_ok(vfunc, vfunc_optimizer, epoch_states,
+                                               critic_batch_size)
+    if params is not None:
+        CRITIC_FIT_STATS["path"] = "kernel"
+        _fit_critic_kernel(params, vfunc_optimizer, epoch_states, epoch_targets, critic_iters,
+                           critic_batch_size)
+        return
+    CRITIC_FIT_STATS["path"] = "host"
     if optimizer == 'lbfgs':
         def compute_vfunc_loss():
             vfunc_optimizer.zero_grad()

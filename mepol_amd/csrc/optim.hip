@@ -14,7 +14,8 @@
 // update (graph warm-up).  Optional snapshot pointers receive p, m, v as they were before the
 // update (the device iteration's shadow of theta and its moment snapshot, so a speculative
 // replay can be undone without separate copy launches).
-#include "common.hpp"
+// Adam's element arithmetic is adam_math.hpp's adam_element, shared with critic_fit.hip.
+#include "adam_math.hpp"
 
 #include <algorithm>
 
@@ -47,20 +48,19 @@ __global__ __launch_bounds__(256) void adam_kernel(Tensors t, const double* __re
   double* ps = t.ps[ti];
   double* ms = t.ms[ti];
   double* vs = t.vs[ti];
-  const double step_size = scal[1], bc2_sqrt = scal[2], b1 = scal[3], b2 = scal[4], eps = scal[5];
-  const double w1 = 1.0 - b1, w2 = 1.0 - b2, neg_step = -step_size;
+  const AdamStep st = adam_step(scal[1], scal[2], scal[3], scal[4], scal[5]);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    const double gi = g[i], m0 = m[i], v0 = v[i], p0 = p[i];
+    const double gi = g[i];
+    double mi = m[i], vi = v[i];
+    const double p0 = p[i];
     if (ps) ps[i] = p0;
-    if (ms) ms[i] = m0;
-    if (vs) vs[i] = v0;
-    const double mi = m0 + w1 * (gi - m0);
-    const double vi = v0 * b2 + w2 * (gi * gi);
-    const double d = sqrt(vi) / bc2_sqrt + eps;
+    if (ms) ms[i] = mi;
+    if (vs) vs[i] = vi;
+    const double d = adam_moments(st, gi, mi, vi);
     m[i] = mi;
     v[i] = vi;
-    p[i] = p0 + neg_step * (mi / d);
+    p[i] = adam_param(st, p0, mi, d);
   }
 }
 

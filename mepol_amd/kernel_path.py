@@ -106,3 +106,72 @@ def goal_sampler(env, policy):
         return None
     layers = _rollout_mlp_layers(policy, env.num_features, 2)
     return None if layers is None else (env.get_reward, layers)
+
+
+def critic_fit_refusal(vfunc, vfunc_optimizer, states, critic_batch_size):
+    """(reason, params) of TRPO's critic-fit gate: reason is None and params the critic's six
+    tensors [W1, b1, W2, b2, W3, b3] when the one-launch kernel (ops.critic_fit) takes the fit,
+    else reason says in a few words why not and params is None.  The checks run from the
+    switch and the network's form to the optimizer and, last, the device."""
+    if os.environ.get("MEPOL_CRITIC_FIT", "kernel") == "host":
+        return "MEPOL_CRITIC_FIT=host", None
+    kinds = (nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear)
+    if type(vfunc) is not nn.Sequential or len(vfunc) != len(kinds):
+        return "not Linear/ReLU/Linear/ReLU/Linear: layer count", None
+    if any(type(m) is not k for m, k in zip(vfunc, kinds)):
+        return "not Linear/ReLU/Linear/ReLU/Linear: layer types", None
+    l1, l2, l3 = vfunc[0], vfunc[2], vfunc[4]
+    if any(l.bias is None for l in (l1, l2, l3)) or l3.out_features != 1:
+        return "a layer without bias, or an output wider than 1", None
+    nf, h0, h1 = l1.in_features, l1.out_features, l2.out_features
+    batch = int(critic_batch_size)
+    if not (1 <= nf <= ops.CRITIC_FIT_MAX_FEATURES and 1 <= h0 <= ops.CRITIC_FIT_MAX_WIDTH
+            and 1 <= h1 <= ops.CRITIC_FIT_MAX_WIDTH and 1 <= batch <= ops.CRITIC_FIT_MAX_BATCH):
+        return "shape outside the kernel's limits", None
+    if states.dim() != 2 or states.shape[1] != nf or states.shape[0] < batch:
+        return "states do not fit the critic, or hold less than one mini-batch", None
+    params = [l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias]
+    if states.dtype != torch.float64 or any(p.dtype != torch.float64 for p in params):
+        return "dtype is not float64", None
+    if type(vfunc_optimizer) is not torch.optim.Adam:
+        return "optimizer is not torch.optim.Adam", None
+    if len(vfunc_optimizer.param_groups) != 1:
+        return "more than one parameter group", None
+    g = vfunc_optimizer.param_groups[0]
+    if len(g["params"]) != 6 or any(a is not b for a, b in zip(g["params"], params)):
+        return "the optimizer does not hold exactly the critic's tensors", None
+    if (tuple(g["betas"]) != (0.9, 0.999) or g["eps"] != 1e-8
+            or not isinstance(g["lr"], (int, float))):
+        return "betas, eps or lr are not Adam's plain defaults", None
+    if g["weight_decay"] != 0 or g.get("decoupled_weight_decay", False):
+        return "weight decay", None
+    if g["amsgrad"]:
+        return "amsgrad", None
+    if g["maximize"] or g.get("capturable", False):
+        return "maximize or capturable", None
+    # the optimizer's state: none yet, or Adam's own for all six tensors at one step number
+    st = [vfunc_optimizer.state.get(p, {}) for p in params]
+    if any(len(s) for s in st):
+        if (any(set(s) != {"step", "exp_avg", "exp_avg_sq"} for s in st)
+                or len({float(s["step"]) for s in st}) != 1):
+            return "optimizer state is not Adam's at one step number", None
+        for s, p in zip(st, params):
+            for t in (s["exp_avg"], s["exp_avg_sq"]):
+                if (t.dtype != p.dtype or t.device != p.device or t.shape != p.shape
+                        or not t.is_contiguous()):
+                    return "optimizer moments do not match the parameters", None
+    if (not states.is_cuda or any(p.device != states.device for p in params)
+            or not all(p.is_contiguous() for p in params)):
+        return "not on the GPU (or not contiguous)", None
+    return None, params
+
+
+def critic_fit_ok(vfunc, vfunc_optimizer, states, critic_batch_size):
+    """The critic's six tensors [W1, b1, W2, b2, W3, b3] when TRPO's critic fit
+    (algorithms/trpo.py _fit_critic) takes the one-launch kernel (ops.critic_fit), else None: an
+    nn.Sequential of exactly Linear / ReLU / Linear / ReLU / Linear(., 1) within the kernel's
+    limits, f64 on the GPU like the states; a torch.optim.Adam with one parameter group holding
+    exactly those tensors, default betas and eps, no weight decay, amsgrad and maximize off, not
+    capturable.  MEPOL_CRITIC_FIT=host turns the kernel path off.  critic_fit_refusal gives the
+    reason."""
+    return critic_fit_refusal(vfunc, vfunc_optimizer, states, critic_batch_size)[1]

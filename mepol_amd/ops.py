@@ -731,6 +731,76 @@ def optim_step(kind, params, grads, exp_avg, exp_avg_sq, scalars, snapshot=None)
          sizes, ptr(scalars), sp[0], sp[1], sp[2], _stream())
 
 
+CRITIC_FIT_MAX_FEATURES, CRITIC_FIT_MAX_WIDTH, CRITIC_FIT_MAX_BATCH = 16, 64, 64
+
+
+def critic_fit_plan(nf, h0, h1, batch):
+    """{threads, lds_bytes, accepted} of mepol_critic_fit at this shape (host only)."""
+    t, l, ok = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    call("mepol_critic_fit_plan_info", int(nf), int(h0), int(h1), int(batch), ctypes.byref(t),
+         ctypes.byref(l), ctypes.byref(ok))
+    return {"threads": t.value, "lds_bytes": l.value, "accepted": bool(ok.value)}
+
+
+def adam_step_scalars(lr, betas, first_step, n_steps):
+    """[n_steps, 2] f64 host tensor of (lr / bias_correction1, sqrt(bias_correction2)) for step
+    numbers first_step .. first_step + n_steps - 1, in Python f64 as torch.optim.Adam computes
+    them (the convention of optim_step's scalars)."""
+    beta1, beta2 = betas
+    rows = []
+    for k in range(int(n_steps)):
+        step = float(first_step + k)
+        rows.append((lr / (1 - beta1 ** step), (1 - beta2 ** step) ** 0.5))
+    return torch.tensor(rows, dtype=torch.float64).reshape(int(n_steps), 2)
+
+
+def critic_fit(states, targets, index, batch, params, exp_avg, exp_avg_sq, lr, betas=(0.9, 0.999),
+               eps=1e-8, first_step=1, loss_out=None):
+    """n_steps = index.numel() // batch Adam steps of the critic's mini-batch fit in one launch
+    (mepol_critic_fit): step s fits rows index[s * batch : (s + 1) * batch] of states [N, nf] /
+    targets [N] to loss mean((v(x) - t)^2).  params = [W1, b1, W2, b2, W3, b3] of Linear(nf, h0)
+    -> ReLU -> Linear(h0, h1) -> ReLU -> Linear(h1, 1), exp_avg / exp_avg_sq their Adam moments:
+    contiguous f64 device tensors, updated in place.  index is int32 on the device with entries
+    in [0, N).  first_step is the number of the first step (torch's state['step'] + 1): it sets
+    the bias corrections.  Returns loss_out [n_steps]: each step's loss before its update."""
+    params, exp_avg, exp_avg_sq = list(params), list(exp_avg), list(exp_avg_sq)
+    _require_device(states, targets, index, loss_out, *params, *exp_avg, *exp_avg_sq)
+    if len(params) != 6 or len(exp_avg) != 6 or len(exp_avg_sq) != 6:
+        raise ValueError("critic_fit: six parameter tensors and their moments are needed")
+    for t in [states, targets] + params + exp_avg + exp_avg_sq:
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.device != states.device:
+            raise ValueError("critic_fit needs contiguous f64 tensors on one device")
+    if index.dtype != torch.int32 or not index.is_contiguous() or index.device != states.device:
+        raise ValueError("critic_fit: index must be a contiguous int32 tensor on the device")
+    if states.dim() != 2 or targets.dim() != 1 or targets.shape[0] != states.shape[0]:
+        raise ValueError("critic_fit: states [N, nf] and targets [N] are needed")
+    n, nf = states.shape
+    W1, b1, W2, b2, W3, b3 = params
+    h0, h1 = W1.shape[0], W2.shape[0]
+    shapes = [(h0, nf), (h0,), (h1, h0), (h1,), (1, h1), (1,)]
+    for lst in (params, exp_avg, exp_avg_sq):
+        if [tuple(t.shape) for t in lst] != shapes:
+            raise ValueError(f"critic_fit: tensors of shapes {shapes} are needed, in that order")
+    batch = int(batch)
+    # the shape limits (batch < 1 among them) are the library's to refuse, with its message
+    n_steps = index.numel() // batch if batch > 0 else 1
+    if n_steps < 1 or (batch > 0 and index.numel() % batch):
+        raise ValueError("critic_fit: index must hold a whole number (>= 1) of mini-batches")
+    dev = states.device
+    scal = adam_step_scalars(lr, betas, first_step, n_steps).to(dev)
+    if loss_out is None:
+        loss_out = torch.empty(n_steps, dtype=torch.float64, device=dev)
+    elif (loss_out.dtype != torch.float64 or not loss_out.is_contiguous()
+          or loss_out.numel() != n_steps):
+        raise ValueError("critic_fit: loss_out must be a contiguous f64 tensor of n_steps")
+    arr = ctypes.c_void_p * 6
+    call("mepol_critic_fit", ptr(states), ptr(targets), n, ptr(index), n_steps, batch, nf, h0, h1,
+         arr(*[t.data_ptr() for t in params]), arr(*[t.data_ptr() for t in exp_avg]),
+         arr(*[t.data_ptr() for t in exp_avg_sq]), ptr(scal), float(betas[0]), float(betas[1]),
+         float(eps), ptr(loss_out), _stream())
+    return loss_out
+
+
 def step_mountaincar(state, action):
     """In-place batched MountainCar step: state f64 [n,2], action f64 [n, a>=1]."""
     _require_device(state, action)

@@ -13,7 +13,10 @@ Per epoch, the median [min, max] over --reps epochs after --warmup:
                   --host_reps and a short warm-up batch;
   process_batch   ops.gae + ops.standardize over the sampled batch (values from the critic);
   trpo_step       the policy update;
-  critic_fit      the reference's Adam fit, 5 passes over mini-batches of 64.
+  critic_fit      the reference's Adam fit, 5 passes over mini-batches of 64, as _fit_critic runs
+                  it: one launch of ops.critic_fit (the row says which path it took);
+  critic_fit_host the same fit from the same critic on the reference's DataLoader loop in the
+                  same process (MEPOL_CRITIC_FIT=host): one torch step per mini-batch.
 Sampling is timed at two policies, since the termination frequency changes the round count: the
 pre-trained-like weights of tests/golden/policy_pretrained_gw.npz and a random initialisation.
 The other parts are timed on the random policy's batch.  Wall-clock times between device
@@ -116,7 +119,8 @@ def main(argv=None):
     m, _, nf = states.shape
     theta0 = {k: v.clone() for k, v in policy.state_dict().items()}
     critic0 = {k: v.clone() for k, v in vfunc.state_dict().items()}
-    parts = {"process_batch": [], "trpo_step": [], "critic_fit": []}
+    parts = {"process_batch": [], "trpo_step": [], "critic_fit": [], "critic_fit_host": []}
+    fit_paths, fit_steps = set(), 5 * (B // 64)
     for i in range(args.warmup + args.reps):
         policy.load_state_dict(theta0)
         vfunc.load_state_dict(critic0)
@@ -127,11 +131,23 @@ def main(argv=None):
             states, actions, rewards, lens, done, values, GAMMA, LAMBD))
         t_step, _ = _wall(lambda: T.trpo_step(policy, es, ea, eadv, KL_THRESH,
                                               cg_iters=args.cg_iters, cg_damping=CG_DAMPING))
+        os.environ.pop("MEPOL_CRITIC_FIT", None)
         t_fit, _ = _wall(lambda: T._fit_critic(vfunc, opt, "adam", es, et, 1e-3, 5, 64))
+        fit_paths.add(T.CRITIC_FIT_STATS["path"])
+        vfunc.load_state_dict(critic0)
+        opt = torch.optim.Adam(vfunc.parameters(), lr=1e-2)
+        os.environ["MEPOL_CRITIC_FIT"] = "host"
+        t_host, _ = _wall(lambda: T._fit_critic(vfunc, opt, "adam", es, et, 1e-3, 5, 64))
+        assert T.CRITIC_FIT_STATS["path"] == "host"
+        os.environ.pop("MEPOL_CRITIC_FIT", None)
         if i >= args.warmup:
-            for k, t in (("process_batch", t_pb), ("trpo_step", t_step), ("critic_fit", t_fit)):
+            for k, t in (("process_batch", t_pb), ("trpo_step", t_step), ("critic_fit", t_fit),
+                         ("critic_fit_host", t_host)):
                 parts[k].append(t)
     rows.update({k: _stats(v) for k, v in parts.items()})
+    for k in ("critic_fit", "critic_fit_host"):
+        rows[k].update(steps=fit_steps, us_per_step=1e3 * rows[k]["median_ms"] / fit_steps)
+    rows["critic_fit"]["path"] = "/".join(sorted(fit_paths))
     result = {"shape": {"batch_size": B, "traj_len": L, "hidden": [300, 300],
                         "cg_iters": args.cg_iters, "kl_thresh": KL_THRESH},
               "run": {"reps": args.reps, "warmup": args.warmup, "host_reps": args.host_reps},

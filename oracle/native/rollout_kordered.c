@@ -20,8 +20,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+/* the reference's clips (min(max(a, lo), hi) in Python, np.clip): NaN stays NaN, +-inf clips */
+static double clip_action(double a, double lo, double hi) {
+  return a < lo ? lo : (a > hi ? hi : a);
+}
+
 static void mc_step(double* p, double* v, double a0) {
-  const double force = fmin(fmax(a0, -1.0), 1.0);
+  const double force = clip_action(a0, -1.0, 1.0);
   *v = *v + (force * 0.0015 - 0.0025 * cos(3.0 * *p));
   if (*v > 0.07) *v = 0.07;
   if (*v < -0.07) *v = -0.07;
@@ -40,7 +45,7 @@ static int inside(double x, double y, double x0, double x1, double y0, double y1
 }
 
 static void gw_step(float* sx, float* sy, double ax, double ay) {
-  const double dx = fmin(fmax(ax, -0.2), 0.2), dy = fmin(fmax(ay, -0.2), 0.2);
+  const double dx = clip_action(ax, -0.2, 0.2), dy = clip_action(ay, -0.2, 0.2);
   const double x = (double)*sx, y = (double)*sy;
   double nx = x + dx, ny = y + dy;
   const double h = 1.25, w = 2.5, D = 6.0;

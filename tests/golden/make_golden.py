@@ -19,6 +19,9 @@ Fixtures:
                    (src/policy.py:16-67), incl. the pretrained/grid_world weights.
   env_*.npz        MountainCar / GridWorld single steps (mountain_car_wall.py:13-45,
                    gridworld_continuous.py:128-154), edge cases included.
+  env_*_edges.npz  the same single steps on hand-placed rows (`name` labels each): landings on
+                   every wall side and corner, the outer bound, the doors, the action clip's
+                   ends, non-finite actions, and MountainCar's four clamps, reset and goal clip.
   control_*.npz    mepol() off-policy control flow (mepol.py:404-499) driven by scripted
                    (loss, KL) sequences: learning rates, accepts, backtracks, CSV rows.
   heatmap_*.npz    get_heatmap (mepol.py:19-67) + Discretizer (src/envs/discretizer.py) over
@@ -36,7 +39,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference"
 
 
-def _save(name, **arrays):
+def _save(name, /, **arrays):  # (positional only: the edge fixtures have a `name` array)
     path = os.path.join(HERE, name)
     np.savez_compressed(path, **arrays)
     print(f"wrote {name}: {os.path.getsize(path) / 1e3:.0f} kB")
@@ -252,6 +255,166 @@ def gen_env(GridWorldContinuous, MountainCarContinuous):
     _save("env_gw.npz", S=S, A=A, NS=NS)
 
 
+GW_WALLS = [(-1.25, 1.25, -2.5, 2.5), (-2.5, -1.25, -1.25, 1.25), (1.25, 2.5, -1.25, 1.25),
+            (-6.0, -3.5, -1.25, 1.25), (-1.25, 1.25, -6.0, -3.5), (3.5, 6.0, -1.25, 1.25),
+            (-1.25, 1.25, 3.5, 6.0)]  # (xmin, xmax, ymin, ymax): where the rows are PLACED
+
+
+def _gw_edge_rows():
+    """(name, state, action) of the GridWorld boundary rows: every coordinate and move is dyadic
+    unless the label says otherwise, so state + move is exact in f64.  The walls above only place
+    the rows; what each row does is whatever the reference's step returns."""
+    f32 = np.float32
+    up = lambda v: float(np.nextafter(f32(v), f32(np.inf)))  # noqa: E731
+    dn = lambda v: float(np.nextafter(f32(v), f32(-np.inf)))  # noqa: E731
+    m = 0.125
+    rows = []
+
+    def others_hit(w, x, y):
+        return any(a <= x <= b and c <= y <= d for i, (a, b, c, d) in enumerate(GW_WALLS) if i != w)
+
+    def approach(land, out):
+        """Start one move outside `land` in direction `out` (from the inside where that start
+        would lie beyond the outer bound) and the move that leads back onto it."""
+        s = land + out * m
+        if abs(s) >= 6:
+            s = land - out * m
+        return s, land - s
+
+    for w, (x0, x1, y0, y1) in enumerate(GW_WALLS):
+        for side, fixed, out, lo, hi in (("x0", x0, -1, y0, y1), ("x1", x1, 1, y0, y1),
+                                         ("y0", y0, -1, x0, x1), ("y1", y1, 1, x0, x1)):
+            xs = side[0] == "x"
+            pt = (lambda f, o: (f, o)) if xs else (lambda f, o: (o, f))  # noqa: E731
+            # a point of the side that no other wall holds, where there is one
+            cand = [lo + (hi - lo) * k / 16 for k in (13, 3, 8, 11, 5, 15, 1)]
+            free = [c for c in cand if not others_hit(w, *pt(fixed, c)) and abs(c) < 6]
+            o = (free or cand)[0]
+            s, mv = approach(fixed, out)
+            rows.append((f"wall{w}/side_{side}", pt(s, o), pt(mv, 0.0)))
+            # twins: the same move with the other coordinate one f32 ulp outside the side's ends
+            rows.append((f"wall{w}/side_{side}/twin_hi", pt(s, up(hi)), pt(mv, 0.0)))
+            rows.append((f"wall{w}/side_{side}/twin_lo", pt(s, dn(lo)), pt(mv, 0.0)))
+        for cx, ox in ((x0, -1), (x1, 1)):
+            for cy, oy in ((y0, -1), (y1, 1)):
+                sx, mx = approach(cx, ox)
+                sy, my = approach(cy, oy)
+                rows.append((f"wall{w}/corner_{'x0' if ox < 0 else 'x1'}{'y0' if oy < 0 else 'y1'}",
+                             (sx, sy), (mx, my)))
+        # a landing 2^-30 outside the upper sides: not inside in f64, on the side once stored as f32
+        ox, oy = x0 + (x1 - x0) * 13 / 16, y0 + (y1 - y0) * 13 / 16
+        far = 2.0 ** -30
+        rows.append((f"round/wall{w}_x1", (x1 + m if x1 + m < 6 else x1 - m, oy),
+                     ((-m + far) if x1 + m < 6 else (m + far), 0.0)))
+        rows.append((f"round/wall{w}_y1", (ox, y1 + m if y1 + m < 6 else y1 - m),
+                     (0.0, (-m + far) if y1 + m < 6 else (m + far))))
+    # outer bound
+    below6 = dn(6.0)
+    for sg, c in ((1.0, "+"), (-1.0, "-")):
+        rows.append((f"bound/on_x{c}", (sg * 5.875, 3.0), (sg * m, 0.0)))
+        rows.append((f"bound/on_y{c}", (-3.0, sg * 5.875), (0.0, sg * m)))
+        rows.append((f"bound/below_x{c}", (sg * (below6 - m), 3.0), (sg * m, 0.0)))
+        rows.append((f"bound/below_y{c}", (-3.0, sg * (below6 - m)), (0.0, sg * m)))
+        rows.append((f"bound/beyond_x{c}", (sg * 5.875, 3.0), (sg * 0.1875, 0.0)))
+        rows.append((f"bound/beyond_y{c}", (-3.0, sg * 5.875), (0.0, sg * 0.1875)))
+    rows.append(("bound/corner", (5.875, 5.875), (m, m)))
+    # the four doors, crossed through their centre: into the gap, and on inside it
+    for nm, cx, cy in (("W", -3.0, 0.0), ("E", 3.0, 0.0), ("S", 0.0, -3.0), ("N", 0.0, 3.0)):
+        if cy == 0.0:
+            rows.append((f"door/{nm}/enter", (cx, 1.375), (0.0, -0.1875)))
+            rows.append((f"door/{nm}/mid", (cx, 0.0625), (0.0, -m)))
+            rows.append((f"door/{nm}/leave", (cx, -1.1875), (0.0, -m)))
+        else:
+            rows.append((f"door/{nm}/enter", (1.375, cy), (-0.1875, 0.0)))
+            rows.append((f"door/{nm}/mid", (0.0625, cy), (-m, 0.0)))
+            rows.append((f"door/{nm}/leave", (-1.1875, cy), (-m, 0.0)))
+    # starts inside a wall
+    rows.append(("inside/zero_move", (0.0, 0.0), (0.0, 0.0)))
+    rows.append(("inside/move_within", (0.0, 0.0), (m, -m)))
+    rows.append(("inside/move_out", (1.1875, 2.0), (m, 0.0)))
+    rows.append(("inside/move_out_outer", (-5.0, 1.1875), (0.0, m)))
+    # actions, from a free start (the sums with 0.2 round in f64: not dyadic)
+    md = 0.2
+    acts = [("+max", md), ("-max", -md), ("+max_below", np.nextafter(md, 0.0)),
+            ("+max_above", np.nextafter(md, 1.0)), ("-max_below", -np.nextafter(md, 0.0)),
+            ("-max_above", -np.nextafter(md, 1.0)), ("+zero", 0.0), ("-zero", -0.0),
+            ("+huge", 1e300), ("-huge", -1e300), ("+inf", np.inf), ("-inf", -np.inf),
+            ("+subnormal", 5e-324), ("-subnormal", -2.0 ** -1040)]
+    for nm, a in acts:
+        rows.append((f"action/x{nm}", (-5.0, -5.0), (a, 0.0625)))
+        rows.append((f"action/y{nm}", (-5.0, -5.0), (-0.0625, a)))
+    rows.append(("action/inf_both", (-5.0, -5.0), (np.inf, -np.inf)))
+    rows.append(("nan/x", (-5.0, -5.0), (np.nan, 0.1)))
+    rows.append(("nan/y", (-5.0, -5.0), (0.1, np.nan)))
+    rows.append(("nan/both", (-5.0, -5.0), (np.nan, np.nan)))
+    rows.append(("nan/x_in_wall", (0.0, 0.0), (np.nan, 0.1)))
+    rows.append(("nan/y_at_bound", (5.875, 3.0), (0.2, np.nan)))
+    return rows
+
+
+def _mc_edge_rows():
+    """(name, (p, v), a) of the MountainCar boundary rows."""
+    rows = []
+    one = 1.0
+    for nm, a in (("+1", one), ("-1", -one), ("+1_below", np.nextafter(one, 0.0)),
+                  ("+1_above", np.nextafter(one, 2.0)), ("-1_below", -np.nextafter(one, 0.0)),
+                  ("-1_above", -np.nextafter(one, 2.0)), ("+inf", np.inf), ("-inf", -np.inf),
+                  ("+zero", 0.0), ("-zero", -0.0)):
+        # (no finite force above 1.3e154: the reference's reward line squares it with math.pow)
+        rows.append((f"force/{nm}", (-0.5, 0.0), a))
+        rows.append((f"force/{nm}/moving", (-0.9, -0.03), a))
+    rows.append(("nan/rest", (-0.5, 0.0), np.nan))
+    rows.append(("nan/moving", (0.3, 0.05), np.nan))
+    rows.append(("nan/at_min", (-1.2, 0.0), np.nan))
+    for nm, s, a in (
+            ("vmax/past", (-0.5, 0.0699), 1.0), ("vmax/past_far", (-1.0, 0.069), 5.0),
+            ("vmax/start_at", (0.2, 0.07), 5.0),
+            ("vmax/short", (-0.5, 0.068), 1.0),
+            ("vmin/past", (-0.5, -0.0699), -1.0), ("vmin/past_far", (0.0, -0.069), -5.0),
+            ("vmin/start_at", (-0.9, -0.07), -5.0),
+            ("vmin/short", (-0.5, -0.066), -1.0),
+            ("pmax/past", (0.58, 0.07), 1.0), ("pmax/past_slow", (0.6, 0.02), 1.0),
+            ("goal/landing", (0.44, 0.05), 1.0), ("goal/landing_top", (0.53, 0.069), -1.0),
+            ("goal/short", (0.38, 0.05), 1.0), ("goal/at", (0.45, 0.0), 1.0),
+            ("goal/back", (0.45, 0.0), -1.0),
+            ("pmin/past", (-1.19, -0.06), -1.0), ("pmin/past_pushed", (-1.19, -0.06), 1.0),
+            ("pmin/at_v_neg", (-1.2, -0.01), -1.0), ("pmin/short", (-1.1, -0.06), -1.0),
+            ("pmin/start_v_pos", (-1.2, 0.01), 1.0),
+            ("pmin/start_v_pos_pulled", (-1.2, 0.03), -1.0), ("pmin/start_rest", (-1.2, 0.0), 1.0),
+            ("pmin/start_v_neg_pushed", (-1.2, -0.001), 1.0)):
+        rows.append((nm, s, a))
+    return rows
+
+
+def gen_env_edges(GridWorldContinuous, MountainCarContinuous):
+    """One reference step per hand-placed boundary row (env_gw.npz / env_mc.npz are random points,
+    which never land on a wall side, a clamp or a non-finite action)."""
+    env = GridWorldContinuous()
+    rows = _gw_edge_rows()
+    S = np.array([r[1] for r in rows], dtype=np.float64)
+    assert np.array_equal(S.astype(np.float32).astype(np.float64), S)  # f32 states, exactly
+    S = S.astype(np.float32)
+    A = np.array([r[2] for r in rows], dtype=np.float64)
+    NS = np.zeros_like(S)
+    with np.errstate(all="ignore"):
+        for i in range(len(S)):
+            env.state = S[i].copy()
+            ns, _, _, _ = env.step(A[i].copy())
+            NS[i] = ns
+    _save("env_gw_edges.npz", S=S, A=A, NS=NS, name=np.array([r[0] for r in rows]))
+
+    env = MountainCarContinuous()
+    rows = _mc_edge_rows()
+    S = np.array([r[1] for r in rows], dtype=np.float64)
+    A = np.array([[r[2]] for r in rows], dtype=np.float64)
+    NS = np.zeros_like(S)
+    for i in range(len(S)):
+        env.state = S[i].copy()
+        ns, _, _, _ = env.step(A[i].copy())
+        NS[i] = ns
+    _save("env_mc_edges.npz", S=S, A=A, NS=NS, name=np.array([r[0] for r in rows]))
+
+
 def gen_control(M, GaussianPolicy, torch):
     """Drive the reference mepol() loop with scripted (loss, KL) values and record its decisions."""
     scenarios = {
@@ -416,6 +579,8 @@ def main():
     torch.set_num_threads(8)
     if not only or "env" in only:
         gen_env(GridWorldContinuous, MountainCarContinuous)
+    if not only or "env_edges" in only:
+        gen_env_edges(GridWorldContinuous, MountainCarContinuous)
     if not only or "policy" in only:
         gen_policy(GaussianPolicy, torch)
     if not only or "knn" in only:

@@ -34,8 +34,9 @@ extern "C" {
 
 /* Bumped on every incompatible change of the signatures below (2: mepol_rollout_mlp takes a
  * workspace; mepol_gemm_dpp removed; 3: mepol_iw_normalize_gathered takes the per-rank
- * trajectory sums).  Additions keep the number: the *_plan_info queries, and mepol_critic_fit
- * with mepol_critic_fit_plan_info, came in at 4.  mepol_abi_version() returns the library's
+ * trajectory sums).  Additions keep the number: the *_plan_info queries, mepol_critic_fit with
+ * mepol_critic_fit_plan_info, and mepol_rollout_deep_goal with
+ * mepol_rollout_deep_goal_plan_info, came in at 4.  mepol_abi_version() returns the library's
  * value. */
 #define MEPOL_ABI_VERSION 4
 
@@ -246,6 +247,28 @@ int mepol_rollout_goal_workspace_size(int env_id, int64_t n, int64_t T, int h0, 
  * goal-mode kernel's own occupancy; k_chunks is the same. */
 int mepol_rollout_goal_plan_info(int64_t n, int h0, int h1, int a_dim, int* workgroups_per_traj,
                                  int* k_chunks);
+/* mepol_rollout_goal for the policies of mepol_rollout_deep (3 <= n_hidden <= 6, widths a HOST
+ * array, Wt / bt packed as there): the same hit test, episode results and fully defined outputs,
+ * and up to the end of each episode the recorded states and actions are the bits
+ * mepol_rollout_deep records.  One workgroup per trajectory, which leaves at the episode's end.
+ * env_id 0 returns MEPOL_ERR_UNSUPPORTED; a_dim != 2, a NaN goal, a radius that is not >= 0, a
+ * shape outside mepol_rollout_deep's and a null pointer MEPOL_ERR_BAD_ARG; n <= 0 or T <= 0
+ * returns 0 without a launch.  The workspace (nullable) is mepol_rollout_deep_workspace_size's:
+ * the error-word header, zeroed by every call and never set (MEPOL_ERR_WORKSPACE if smaller). */
+int mepol_rollout_deep_goal(int env_id, int n_hidden, const int* widths, const double* W1,
+                            const double* b1, const double* Wt, const double* bt,
+                            const double* Wm, const double* bm, const double* log_std, int a_dim,
+                            const float* init32, const double* noise, int64_t n, int64_t T,
+                            float goal_x, float goal_y, double radius, float* states_rec,
+                            float* actions_rec, float* rewards_rec, int32_t* len_out,
+                            int32_t* done_out, void* workspace, size_t workspace_bytes,
+                            void* stream);
+/* Workgroups (= trajectories) of mepol_rollout_deep_goal the device holds at once at this shape:
+ * the goal-mode kernel's occupancy at the launcher's block size and dynamic LDS, times the
+ * number of compute units.  A round of at most that many trajectories runs as one wave of
+ * workgroups. */
+int mepol_rollout_deep_goal_plan_info(int n_hidden, const int* widths, int a_dim,
+                                      int* resident_workgroups);
 /* The step budget of collect_sample_batch (`steps == batch_size`, trpo.py:98-140) over a batch
  * that was rolled out in parallel: trajectories are taken in index order while the running sum of
  * len [n] is below `budget`, and the last one is cut so that the sum equals it.  len_out [n] = the

@@ -121,6 +121,12 @@ SIGNATURES = {
                                           ctypes.POINTER(_c_sz)],
     "mepol_rollout_goal_plan_info": [_c_i64, _c_int, _c_int, _c_int, ctypes.POINTER(_c_int),
                                      ctypes.POINTER(_c_int)],
+    "mepol_rollout_deep_goal": [_c_int, _c_int, ctypes.POINTER(_c_int), _c_vp, _c_vp, _c_vp,
+                                _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64,
+                                ctypes.c_float, ctypes.c_float, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp,
+                                _c_vp, _c_vp, _c_sz, _c_vp],
+    "mepol_rollout_deep_goal_plan_info": [_c_int, ctypes.POINTER(_c_int), _c_int,
+                                          ctypes.POINTER(_c_int)],
     "mepol_traj_budget": [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],
     "mepol_gae": [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_dbl, _c_dbl, _c_vp,
                   _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],

@@ -145,11 +145,13 @@ def _rollout_graph(policy, env_id, init, T, a_dim, nf):
 ROLLOUT_DEEP_MAX_WORDS = 2 * 512 * 512
 
 
-def _rollout_layers(policy, nf, a_dim, deep):
+def _rollout_layers(policy, nf, a_dim, deep, word_cap=True):
     """[(W_1, b_1), ..., (W_L, b_L)] when a one-launch rollout kernel covers the policy, an
     nf = 2 -> [h_1 .. h_L] -> a ReLU MLP in f64 with h <= 512 (odd widths included) and a <= 8,
     else None.  L = 2 (csrc/envs.hip), or with deep L = 3 to 6 (csrc/rollout_deep.hip) and at most
-    ROLLOUT_DEEP_MAX_WORDS weight words behind layer 1: where that kernel is the faster one."""
+    ROLLOUT_DEEP_MAX_WORDS weight words behind layer 1: where that kernel is the faster one.
+    word_cap=False drops that last condition, for a caller whose only alternative is the host
+    loop (kernel_path.goal_sampler)."""
     if (os.environ.get("MEPOL_ROLLOUT_FUSED", "1") == "0" or nf != kernel_path.ROLLOUT_FEATURES
             or a_dim > kernel_path.ROLLOUT_MAX_ACTIONS):
         return None
@@ -162,7 +164,7 @@ def _rollout_layers(policy, nf, a_dim, deep):
     if (layers[0].in_features != kernel_path.ROLLOUT_FEATURES
             or max(m.out_features for m in layers) > kernel_path.ROLLOUT_MAX_WIDTH):
         return None
-    if deep:
+    if deep and word_cap:
         cap = int(os.environ.get("MEPOL_ROLLOUT_DEEP_MAX_WORDS", ROLLOUT_DEEP_MAX_WORDS))
         if sum(m.in_features * m.out_features for m in layers[1:]) > cap:
             return None

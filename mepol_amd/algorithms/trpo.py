@@ -25,10 +25,11 @@ F.linear restatement of mu (it must not go through policy._Linear, whose weight 
 kernel call without an autograd graph behind it).
 
 Sampling and batch processing ("TRPO sampling and batch processing").  The reference
-steps one env at a time through policy.predict.  For a GridWorld goal env and the two-layer policy
-(kernel_path.goal_sampler) collect_sample_batch rolls whole rounds of trajectories out in one
-launch each (ops.rollout_goal: termination and the sparse reward inside the kernel), applies the
-reference's step budget on the device (ops.traj_budget) and reads two words per round;
+steps one env at a time through policy.predict.  For a GridWorld goal env and a ReLU policy with
+two to six hidden layers (kernel_path.goal_sampler) collect_sample_batch rolls whole rounds of
+trajectories out in one launch each (ops.rollout_goal for two layers, ops.rollout_deep_goal for
+three to six: termination and the sparse reward inside the kernel), applies the reference's step
+budget on the device (ops.traj_budget) and reads two or three words per round;
 process_batch computes targets, GAE advantages and the packed batch with ops.gae and
 ops.standardize.  Every other env, policy or device takes the reference's sequential loop, and
 CPU tensors a numpy restatement of the same arithmetic.
@@ -388,6 +389,17 @@ def _round_capacity(h0, h1, a_dim, device):
     return _ROUND_CAPACITY[key]
 
 
+def _round_capacity_deep(widths, a_dim, device):
+    """_round_capacity for a policy with 3 to 6 hidden layers: the trajectories (one workgroup
+    each) the device holds at once (ops.rollout_deep_goal_plan), found once per shape and
+    MEPOL_ROLLOUT_KL setting (the resident rows set the kernel's LDS, so its occupancy)."""
+    key = (tuple(widths), a_dim, device, os.environ.get("MEPOL_ROLLOUT_KL"))
+    if key not in _ROUND_CAPACITY:
+        plan = ops.rollout_deep_goal_plan(widths, a_dim)
+        _ROUND_CAPACITY[key] = max(plan["resident_workgroups"], 1)
+    return _ROUND_CAPACITY[key]
+
+
 def _draw_round(base, R, T, a_dim, device, generator):
     """Initial states f32 [R, 2] and action noise f64 [T, R, a] of one round, in this order."""
     init = base.reset_batch_torch(R, device, generator)
@@ -399,9 +411,11 @@ def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, r
     dev = policy.device
     base = unwrap(env)
     a_dim = policy.action_dim
-    (W1, b1), (W2, b2) = layers
+    deep = len(layers) > 2  # ops.rollout_deep_goal: no error word, so no re-run
+    widths = [W.shape[0] for W, _ in layers]
     head = (policy.mean.weight.detach(), policy.mean.bias.detach(), policy.log_std.detach())
-    cap = _round_capacity(W1.shape[0], W2.shape[0], a_dim, dev)
+    cap = (_round_capacity_deep(widths, a_dim, dev) if deep
+           else _round_capacity(*widths, a_dim, dev))
     steps_idx = torch.arange(T + 1, device=dev)
     remaining, rounds, parts = int(batch_size), 0, []
     while remaining > 0:
@@ -414,16 +428,23 @@ def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, r
         rewards = torch.empty((R, T), dtype=torch.float32, device=dev)
         lens = torch.empty(R, dtype=torch.int32, device=dev)
         dones = torch.empty(R, dtype=torch.int32, device=dev)
-        roll = (W1, b1, W2, b2, *head, init.to(torch.float32), noise, goal.goal, goal.radius,
-                states, actions, rewards, lens, dones)
-        err, rerun = ops.rollout_goal(*roll, defer_check=True)
-        kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
-        # the round's one host synchronisation: {trajectories used, steps kept, error word}
-        m, kept, bad = torch.cat([meta, err.to(torch.int64)]).tolist()
-        if bad:
-            rerun()
+        roll = (*head, init.to(torch.float32), noise, goal.goal, goal.radius, states, actions,
+                rewards, lens, dones)
+        if deep:
+            ops.rollout_deep_goal(layers, *roll)
             kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
+            # the round's one host synchronisation: {trajectories used, steps kept}
             m, kept = meta.tolist()
+        else:
+            (W1, b1), (W2, b2) = layers
+            err, rerun = ops.rollout_goal(W1, b1, W2, b2, *roll, defer_check=True)
+            kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
+            # the round's one host synchronisation: {trajectories used, steps kept, error word}
+            m, kept, bad = torch.cat([meta, err.to(torch.int64)]).tolist()
+            if bad:
+                rerun()
+                kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
+                m, kept = meta.tolist()
         rounds += 1
         # a budget-cut last trajectory keeps the state it reached and nothing behind it, as the
         # reference's arrays do; that takes the reward of a goal it reached behind the cut, too
@@ -481,7 +502,8 @@ def collect_sample_batch(env, policy, batch_size, traj_len, num_workers=1, gener
     in one launch each and cut to the remaining budget on the device; taking the first m of a
     parallel round in index order has the distribution of the reference's sequential sampling
     (DESIGN.md).  R = round_traj, or the larger of ceil(remaining / traj_len) and the most
-    trajectories the multi-workgroup rollout holds (_round_capacity).  `generator` seeds the
+    trajectories the multi-workgroup rollout holds (_round_capacity; for 3 to 6 hidden layers
+    the workgroups the device holds at once, _round_capacity_deep).  `generator` seeds the
     draws; `draw(R, T, a, device) -> (init f32 [R, 2], noise f64 [T, R, a])` replaces them
     (tests).  num_workers is ignored there.  Everything else runs the reference's sequential
     loop with one worker."""

@@ -18,12 +18,20 @@
 //   mean layer    per 64-column wave the products Wm[a][j] h_L[j] summed by the xor butterfly
 //                 32, 16, .. 1 (columns past h_L are 0.0), the waves added in order, then + bm[a];
 //   action        mu + noise * exp(log_std), explicit _rn operations.
+//
+// Goal mode (GOAL = true, GridWorld only; mepol_rollout_deep_goal): rollout_mlp_kernel's, with
+// the helpers of goal_mode.hpp.  Thread 0 tests the f32 state after its env step, writes the
+// reward and, on a hit, sets a __shared__ flag before the step's closing barrier; behind that
+// barrier every thread reads the flag and the workgroup leaves the step loop together (no
+// further barrier), then zeroes the rows behind the episode.  Up to each episode's end the
+// records are the bits the GOAL = false instance writes.
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
 
 #include "common.hpp"
 #include "env_step.hpp"
+#include "goal_mode.hpp"
 
 namespace mepol {
 namespace envs {
@@ -81,16 +89,19 @@ __device__ __forceinline__ double deep_column(const double* __restrict__ sw,
   return acc;
 }
 
-template <int ENV>
+template <int ENV, bool GOAL = false>
 __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, const double* __restrict__ Wt,
     const double* __restrict__ bt, const double* __restrict__ Wm, const double* __restrict__ bm,
     const double* __restrict__ log_std, int a_dim, const double* __restrict__ init64,
     const float* __restrict__ init32, const double* __restrict__ noise, int64_t n, int64_t T,
     float* __restrict__ states_rec, float* __restrict__ actions_rec,
-    double* __restrict__ visited, double* __restrict__ final_state, DeepShape sh) {
+    double* __restrict__ visited, double* __restrict__ final_state, DeepShape sh,
+    GoalArgs goal) {
+  static_assert(!GOAL || ENV == 1, "goal mode is GridWorld's");
   extern __shared__ double sW[];  // resident rows of W_2^T .. W_L^T, layer after layer
   __shared__ double sx[2];
+  __shared__ int sgoal;  // GOAL: the step just taken reached the goal (thread 0 writes it)
   __shared__ double shid[2][kDeepMaxH];  // hidden activations, ping-pong
   __shared__ double spart[kDeepMaxH / 64][kDeepMaxA];
   const int64_t i = blockIdx.x;
@@ -132,9 +143,12 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     }
     states_rec[(i * (T + 1)) * 2 + 0] = (float)sx[0];
     states_rec[(i * (T + 1)) * 2 + 1] = (float)sx[1];
+    if constexpr (GOAL) sgoal = 0;
   }
+  int64_t steps = T;  // GOAL: the episode's length
   // thread 0: exp(log_std) once, and the next step's noise loaded a step ahead (its global
-  // latency would otherwise sit on the serial tail of every step)
+  // latency would otherwise sit on the serial tail of every step); the load of step t + 1 is
+  // consumed inside step t (nz = nz_next), so none is pending when a GOAL workgroup leaves
   double sd[kDeepMaxA], nz[kDeepMaxA];
   if (j == 0) {
     for (int a = 0; a < a_dim; ++a) {
@@ -213,12 +227,30 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
         visited[(i * T + t) * 2 + 0] = sx[0];
         visited[(i * T + t) * 2 + 1] = sx[1];
       }
+      if constexpr (GOAL) {
+        const bool hit = goal_hit(gx, gy, goal);
+        goal.rewards[i * T + t] = hit ? 1.f : 0.f;
+        if (hit) sgoal = 1;
+      }
     }
     __syncthreads();
+    if constexpr (GOAL) {
+      if (sgoal) {  // workgroup-uniform: written before the barrier, never cleared
+        steps = t + 1;
+        break;
+      }
+    }
   }
   if (j == 0 && final_state) {
     final_state[2 * i] = sx[0];
     final_state[2 * i + 1] = sx[1];
+  }
+  if constexpr (GOAL) {
+    if (j == 0) {
+      goal.len[i] = (int)steps;
+      goal.done[i] = sgoal;
+    }
+    goal_zero_tail(i, steps, T, a_dim, states_rec, actions_rec, goal.rewards, j, blockDim.x);
   }
 }
 
@@ -237,6 +269,73 @@ static int deep_bad_args(const char* who) {
             "1 <= a_dim <= %d, GridWorld a_dim = 2, no null pointers)",
             who, kDeepMinL, kDeepMaxL, kDeepMaxH, kDeepMaxA);
   return kErrBadArg;
+}
+
+// What a launch at this shape looks like, for the launchers and the occupancy query alike: the
+// kernel's shape argument, the workgroup size and the dynamic LDS.
+struct DeepPlan {
+  DeepShape sh;
+  unsigned threads;
+  size_t lds;
+};
+
+static DeepPlan deep_plan(int n_hidden, const int* widths) {
+  DeepPlan p;
+  DeepShape& sh = p.sh;
+  sh.L = n_hidden;
+  int wmax = 0;
+  for (int l = 0; l < kDeepMaxL; ++l) {
+    sh.h[l] = l < n_hidden ? widths[l] : 0;
+    sh.kl[l] = 0;
+    wmax = std::max(wmax, sh.h[l]);
+  }
+  // leading rows of the packed W_2^T .. W_L^T kept in LDS: whole rows, layer after layer, while
+  // they fit (MEPOL_ROLLOUT_KL caps their number); everything behind them streams
+  const char* klv = getenv("MEPOL_ROLLOUT_KL");
+  int rows_left = klv ? std::max(0, atoi(klv)) : INT_MAX;
+  int words_left = kDeepLdsBytes / (int)sizeof(double);
+  p.lds = 0;
+  for (int l = 1; l < n_hidden; ++l) {
+    const int rows = std::min({sh.h[l - 1], words_left / sh.h[l], rows_left});
+    sh.kl[l] = rows;
+    words_left -= rows * sh.h[l];
+    rows_left -= rows;
+    p.lds += (size_t)rows * sh.h[l] * sizeof(double);
+    if (rows < sh.h[l - 1]) break;
+  }
+  p.threads = (unsigned)((wmax + 63) / 64 * 64);
+  return p;
+}
+
+// mepol_rollout_deep (goal == nullptr) and mepol_rollout_deep_goal (env 1) behind their argument
+// checks: the same plan, workspace header and launch, the kernel's GOAL instance for the second.
+static int deep_run(int env_id, int n_hidden, const int* widths, const double* W1,
+                    const double* b1, const double* Wt, const double* bt, const double* Wm,
+                    const double* bm, const double* log_std, int a_dim, const double* init64,
+                    const float* init32, const double* noise, int64_t n, int64_t T,
+                    float* states_rec, float* actions_rec, double* visited, double* final_state,
+                    const GoalArgs* goal, void* workspace, void* stream) {
+  const DeepPlan p = deep_plan(n_hidden, widths);
+  const GoalArgs ga = goal ? *goal : GoalArgs{};
+  hipStream_t st = (hipStream_t)stream;
+  if (workspace) MEPOL_HIP(hipMemsetAsync(workspace, 0, kDeepWorkspaceBytes, st));
+  const dim3 g((unsigned)n), b(p.threads);
+#define MEPOL_DEEP(E, G)                                                                          \
+  do {                                                                                            \
+    MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<E, G>>(kDeepLdsBytes)));                       \
+    hipLaunchKernelGGL((rollout_deep_kernel<E, G>), g, b, p.lds, st, W1, b1, Wt, bt, Wm, bm,      \
+                       log_std, a_dim, init64, init32, noise, n, T, states_rec, actions_rec,      \
+                       visited, final_state, p.sh, ga);                                           \
+  } while (0)
+  if (goal)
+    MEPOL_DEEP(1, true);
+  else if (env_id == 0)
+    MEPOL_DEEP(0, false);
+  else
+    MEPOL_DEEP(1, false);
+#undef MEPOL_DEEP
+  MEPOL_CHECK_LAUNCH();
+  return 0;
 }
 
 }  // namespace envs
@@ -271,43 +370,66 @@ extern "C" int mepol_rollout_deep(int env_id, int n_hidden, const int* widths, c
               kDeepWorkspaceBytes);
     return kErrWorkspace;
   }
-  DeepShape sh;
-  sh.L = n_hidden;
-  int wmax = 0;
-  for (int l = 0; l < kDeepMaxL; ++l) {
-    sh.h[l] = l < n_hidden ? widths[l] : 0;
-    sh.kl[l] = 0;
-    wmax = std::max(wmax, sh.h[l]);
+  return deep_run(env_id, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, init64, init32,
+                  noise, n, T, states_rec, actions_rec, visited, final_state, nullptr, workspace,
+                  stream);
+}
+
+// mepol_rollout_deep on GridWorld with early termination at a goal: mepol_rollout_goal's episode
+// semantics and outputs for 3 to 6 hidden layers, one workgroup per trajectory (no error word is
+// ever set).  The workspace is mepol_rollout_deep_workspace_size's.
+extern "C" int mepol_rollout_deep_goal(int env_id, int n_hidden, const int* widths,
+                                       const double* W1, const double* b1, const double* Wt,
+                                       const double* bt, const double* Wm, const double* bm,
+                                       const double* log_std, int a_dim, const float* init32,
+                                       const double* noise, int64_t n, int64_t T, float goal_x,
+                                       float goal_y, double radius, float* states_rec,
+                                       float* actions_rec, float* rewards_rec, int32_t* len_out,
+                                       int32_t* done_out, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  if (n <= 0 || T <= 0) return 0;
+  if (a_dim != 2 || !deep_shape_ok(env_id, n_hidden, widths, a_dim) || T > INT32_MAX || !init32 ||
+      !W1 || !b1 || !Wt || !bt || !Wm || !bm || !log_std || !noise || !states_rec ||
+      !actions_rec || !rewards_rec || !len_out || !done_out || !(goal_x == goal_x) ||
+      !(goal_y == goal_y) || !(radius >= 0.0)) {
+    set_error("mepol_rollout_deep_goal: bad arguments (%d <= n_hidden <= %d, 1 <= width <= %d, "
+              "a_dim = 2, radius >= 0, no null pointers)",
+              kDeepMinL, kDeepMaxL, kDeepMaxH);
+    return kErrBadArg;
   }
-  // leading rows of the packed W_2^T .. W_L^T kept in LDS: whole rows, layer after layer, while
-  // they fit (MEPOL_ROLLOUT_KL caps their number); everything behind them streams
-  const char* klv = getenv("MEPOL_ROLLOUT_KL");
-  int rows_left = klv ? std::max(0, atoi(klv)) : INT_MAX;
-  int words_left = kDeepLdsBytes / (int)sizeof(double);
-  size_t lds = 0;
-  for (int l = 1; l < n_hidden; ++l) {
-    const int rows = std::min({sh.h[l - 1], words_left / sh.h[l], rows_left});
-    sh.kl[l] = rows;
-    words_left -= rows * sh.h[l];
-    rows_left -= rows;
-    lds += (size_t)rows * sh.h[l] * sizeof(double);
-    if (rows < sh.h[l - 1]) break;
+  if (env_id != 1) {
+    set_error("mepol_rollout_deep_goal: only GridWorld (env_id 1) has a goal mode");
+    return kErrUnsupported;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (workspace) MEPOL_HIP(hipMemsetAsync(workspace, 0, kDeepWorkspaceBytes, st));
-  const dim3 g((unsigned)n), b((unsigned)((wmax + 63) / 64 * 64));
-#define MEPOL_DEEP(E)                                                                            \
-  do {                                                                                           \
-    MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<E>>(kDeepLdsBytes)));                         \
-    hipLaunchKernelGGL((rollout_deep_kernel<E>), g, b, lds, st, W1, b1, Wt, bt, Wm, bm, log_std, \
-                       a_dim, init64, init32, noise, n, T, states_rec, actions_rec, visited,     \
-                       final_state, sh);                                                         \
-  } while (0)
-  if (env_id == 0)
-    MEPOL_DEEP(0);
-  else
-    MEPOL_DEEP(1);
-#undef MEPOL_DEEP
-  MEPOL_CHECK_LAUNCH();
+  if (workspace && workspace_bytes < kDeepWorkspaceBytes) {
+    set_error("mepol_rollout_deep_goal: workspace of %zu bytes, %zu needed", workspace_bytes,
+              kDeepWorkspaceBytes);
+    return kErrWorkspace;
+  }
+  const GoalArgs goal{goal_x, goal_y, radius, rewards_rec, len_out, done_out};
+  return deep_run(1, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, nullptr, init32,
+                  noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
+                  stream);
+}
+
+// Workgroups of the goal-mode instance the device holds at once for this shape: the kernel's
+// occupancy at the block size and dynamic LDS the launcher chooses, times the CU count.  A round
+// of at most this many trajectories runs in one wave of workgroups.
+extern "C" int mepol_rollout_deep_goal_plan_info(int n_hidden, const int* widths, int a_dim,
+                                                 int* resident_workgroups) {
+  if (a_dim != 2 || !resident_workgroups || !deep_shape_ok(1, n_hidden, widths, a_dim)) {
+    set_error("mepol_rollout_deep_goal_plan_info: bad arguments (%d <= n_hidden <= %d, "
+              "1 <= width <= %d, a_dim = 2)",
+              kDeepMinL, kDeepMaxL, kDeepMaxH);
+    return kErrBadArg;
+  }
+  const DeepPlan p = deep_plan(n_hidden, widths);
+  int dev = 0, cus = 0, per_cu = 0;
+  MEPOL_HIP(hipGetDevice(&dev));
+  MEPOL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<1, true>>(kDeepLdsBytes)));
+  MEPOL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &per_cu, rollout_deep_kernel<1, true>, (int)p.threads, p.lds));
+  *resident_workgroups = per_cu * cus;
   return 0;
 }

@@ -9,6 +9,10 @@ GPU (algorithms/trpo.py):
         --batch_size 24000 --traj_len 1200 --cg_iters 20 --kl_thresh 0.001 \
         --policy_init results/exploration/mepol/<run>/<epoch>-policy
 
+--hidden_sizes N [N ...] (a build extension, as the MEPOL command line's) sets the policy's hidden
+widths, so a policy pre-trained with `mepol --hidden_sizes 300 300 300` loads here; policies with
+two to six ReLU layers sample on the one-launch goal rollouts.
+
 MuJoCo goals (AntEscape, AntNavigate, AntJump, HumanoidUp) keep their specs but need mujoco-py,
 which is outside this build's scope.
 """
@@ -53,7 +57,17 @@ def build_parser():
                    help="The tensorboard directory under which the directory of this experiment is put")
     p.add_argument("--results_dir", type=str, default=None,
                    help="(build extension) root of results/goal_rl; default: ./results/goal_rl")
+    p.add_argument("--hidden_sizes", type=int, nargs="+", default=None, metavar="N",
+                   help="(build extension) hidden layer widths of the policy instead of the "
+                        "experiment spec's; default: the spec's")
     return p
+
+
+def checkpoint_widths(state_dict):
+    """Hidden layer widths a GaussianPolicy checkpoint holds, from its net.<i>.weight keys."""
+    keys = sorted((k for k in state_dict if k.startswith("net.") and k.endswith(".weight")),
+                  key=lambda k: int(k.split(".")[1]))
+    return [int(state_dict[k].shape[0]) for k in keys]
 
 
 def exp_specs():
@@ -96,23 +110,38 @@ def main(argv=None):
     if spec["env_create"] is None:
         print(f"{args.env} needs MuJoCo (mujoco-py), which is outside this build's scope.")
         return 2
+    hidden_sizes = args.hidden_sizes if args.hidden_sizes is not None else spec["hidden_sizes"]
+    if any(w <= 0 for w in hidden_sizes):
+        print("--hidden_sizes needs positive widths.")
+        return 4
     if not torch.cuda.is_available():
         print("mepol_amd needs a ROCm GPU (MI355X); there is no CPU path.")
         return 3
     torch.set_default_dtype(torch.float64)
     device = torch.device("cuda")
     env = spec["env_create"]()
-    policy = GaussianPolicy(num_features=env.num_features, hidden_sizes=spec["hidden_sizes"],
+    policy = GaussianPolicy(num_features=env.num_features, hidden_sizes=hidden_sizes,
                             action_dim=env.action_space.shape[0], activation=spec["activation"],
                             log_std_init=spec["log_std_init"]).to(device)
     vfunc = create_critic(env.num_features).to(device)
     if args.policy_init is not None:
         kind = "MEPOLInit"
-        policy.load_state_dict(torch.load(args.policy_init, map_location=device))
+        checkpoint = torch.load(args.policy_init, map_location=device)
+        own = policy.state_dict()
+        if (set(checkpoint) != set(own)
+                or any(tuple(checkpoint[k].shape) != tuple(v.shape) for k, v in own.items())):
+            held = " ".join(str(w) for w in checkpoint_widths(checkpoint))
+            print(f"--policy_init: the checkpoint holds hidden layers of widths {held}, the "
+                  f"policy has {' '.join(str(w) for w in hidden_sizes)}; pass --hidden_sizes "
+                  f"{held}.")
+            return 4
+        policy.load_state_dict(checkpoint)
     else:
         kind = "RandomInit"
 
     exp_name = f"env={args.env},init={kind}"
+    if args.hidden_sizes is not None:
+        exp_name += ",hidden=" + "x".join(str(w) for w in args.hidden_sizes)
     root = args.results_dir or os.path.join(os.getcwd(), "results", "goal_rl")
     out_path = os.path.join(root, args.tb_dir_name, exp_name + "__" +
                             datetime.now().strftime("%Y_%m_%d_%H_%M_%S") + "__" + str(os.getpid()))
@@ -121,7 +150,7 @@ def main(argv=None):
         f.write("Run info:\n")
         f.write("-" * 10 + "\n")
         for key, value in vars(args).items():
-            if key == "results_dir" and value is None:
+            if key in ("results_dir", "hidden_sizes") and value is None:
                 continue  # absent: the file is the one the reference writes
             f.write(f"{key}={value}\n")
         f.write("-" * 10 + "\n")

@@ -81,13 +81,17 @@ def hidden_backward(dz, x, Ws, hs, dW_out=None, db_out=None, dz_out=None, ws_wgr
 
 
 def goal_sampler(env, policy):
-    """(goal, layers) when TRPO's sampler (algorithms/trpo.py collect_sample_batch) takes the
-    one-launch goal rollout (ops.rollout_goal), else None: an f64 policy on the GPU that
-    algorithms.mepol._rollout_mlp_layers accepts (2 -> [h0, h1] -> a ReLU MLP, widths <= 512),
+    """(goal, layers) when TRPO's sampler (algorithms/trpo.py collect_sample_batch) takes a
+    one-launch goal rollout, else None: an f64 policy on the GPU that
+    algorithms.mepol._rollout_layers accepts (a 2 -> [h_1 .. h_L] -> a ReLU MLP, widths <= 512),
     two actions, and a CustomRewardEnv directly over GridWorldContinuous whose reward is a
-    GridGoal.  goal is that GridGoal (its f32 goal and radius are the kernel's arguments), layers
-    = ((W1, b1), (W2, b2)).  MEPOL_TRPO_SAMPLER=host turns the kernel path off."""
-    from .algorithms.mepol import _rollout_mlp_layers
+    GridGoal.  goal is that GridGoal (its f32 goal and radius are the kernel's arguments).
+    len(layers) names the kernel: the tuple ((W1, b1), (W2, b2)) for ops.rollout_goal, a list
+    [(W1, b1), ..., (W_L, b_L)] of 3 to 6 layers for ops.rollout_deep_goal.  The deep gate has no
+    ROLLOUT_DEEP_MAX_WORDS cap: that is where the deep kernel stops beating MEPOL's replayed
+    per-step graph, and the sampler's only alternative is the host loop.
+    MEPOL_TRPO_SAMPLER=host turns the kernel path off."""
+    from .algorithms.mepol import _rollout_layers, _rollout_mlp_layers
     from .envs.gridworld import GridWorldContinuous
     from .envs.wrappers import CustomRewardEnv, GridGoal
 
@@ -104,7 +108,8 @@ def goal_sampler(env, policy):
             or getattr(policy, "action_dim", None) != 2
             or policy.mean.weight.dtype != torch.float64):
         return None
-    layers = _rollout_mlp_layers(policy, env.num_features, 2)
+    layers = (_rollout_mlp_layers(policy, env.num_features, 2)
+              or _rollout_layers(policy, env.num_features, 2, deep=True, word_cap=False))
     return None if layers is None else (env.get_reward, layers)
 
 

@@ -956,6 +956,59 @@ def rollout_goal(W1, b1, W2, b2, Wm, bm, log_std, init, noise, goal_xy, radius, 
     return None
 
 
+def rollout_deep_goal_plan(widths, a_dim=2):
+    """{"resident_workgroups"}: trajectories of rollout_deep_goal the device holds at once for
+    hidden layers of these widths (the goal-mode kernel's occupancy times the CU count)."""
+    wg = ctypes.c_int()
+    arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
+    call("mepol_rollout_deep_goal_plan_info", len(widths), arr, a_dim, ctypes.byref(wg))
+    return {"resident_workgroups": wg.value}
+
+
+def rollout_deep_goal(layers, Wm, bm, log_std, init, noise, goal_xy, radius, states_rec,
+                      actions_rec, rewards_rec, len_out, done_out, env_id=1):
+    """rollout_goal for a ReLU policy with 3 to 6 hidden layers, layers = [(W1, b1), ..., (W_L,
+    b_L)] as rollout_deep takes them: GridWorld (env_id 1) episodes that end at the first step
+    whose f32 state is within `radius` of goal_xy (reward 1, done) or after T steps, in one launch
+    with one workgroup per trajectory (csrc/rollout_deep.hip, GOAL instance).  Fills states_rec
+    [n,T+1,2], actions_rec [n,T,2], rewards_rec [n,T] (f32, zeros behind each episode's end),
+    len_out and done_out [n] int32; the buffers need no clearing.  There is no error word to
+    check: the workgroups exchange nothing."""
+    _require_device(init, noise, states_rec, actions_rec, rewards_rec, len_out, done_out, Wm, bm,
+                    log_std, *[t for p in layers for t in p])
+    T, n, a_dim = noise.shape
+    (W1, b1), rest = layers[0], layers[1:]
+    fan_in = [2] + [W.shape[0] for W, _ in layers]
+    if (any(tuple(W.shape) != (b.numel(), f) for (W, b), f in zip(layers, fan_in))
+            or tuple(Wm.shape) != (a_dim, fan_in[-1]) or bm.numel() != a_dim
+            or log_std.numel() != a_dim or tuple(init.shape) != (n, 2)
+            or tuple(states_rec.shape) != (n, T + 1, 2) or tuple(actions_rec.shape) != (n, T, a_dim)
+            or tuple(rewards_rec.shape) != (n, T) or len_out.numel() != n
+            or done_out.numel() != n):
+        raise ValueError("rollout_deep_goal: tensor shapes do not fit the policy / batch")
+    f64 = [t for p in layers for t in p] + [Wm, bm, log_std, noise]
+    if (any(t.dtype != torch.float64 for t in f64)
+            or any(t.dtype != torch.float32 for t in (init, states_rec, actions_rec, rewards_rec))
+            or len_out.dtype != torch.int32 or done_out.dtype != torch.int32
+            or not all(t.is_contiguous() for t in (states_rec, actions_rec, rewards_rec, len_out,
+                                                   done_out))):
+        raise ValueError("rollout_deep_goal: f64 policy / noise, f32 contiguous records, int32 "
+                         "len / done")
+    widths = (ctypes.c_int * len(layers))(*[W.shape[0] for W, _ in layers])
+    Wt = torch.cat([W.t().reshape(-1) for W, _ in rest])
+    bt = torch.cat([b.reshape(-1) for _, b in rest])
+    # (contiguous copies stay referenced until the launch is queued)
+    W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
+                                                                     noise))
+    gx, gy = (float(v) for v in goal_xy)
+    ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
+                       a_dim)
+    call("mepol_rollout_deep_goal", env_id, len(layers), widths, ptr(W1), ptr(b1), ptr(Wt),
+         ptr(bt), ptr(Wm), ptr(bm), ptr(log_std), a_dim, ptr(init), ptr(noise), n, T, gx, gy,
+         float(radius), ptr(states_rec), ptr(actions_rec), ptr(rewards_rec), ptr(len_out),
+         ptr(done_out), ptr(ws), ws.numel(), _stream())
+
+
 def traj_budget(lens, dones, budget):
     """The step budget over a parallel batch (mepol_traj_budget): trajectories in index order until
     `budget` steps are kept, the last one cut.  lens, dones: int32 [n] on the device.  Returns

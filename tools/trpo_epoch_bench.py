@@ -3,10 +3,12 @@ batch 24,000, traj_len 1200, policy 2 -> [300, 300] -> 2, cg_iters 20, kl_thresh
 
     python tools/trpo_epoch_bench.py                      JSON to profiles/trpo_epoch_bench.json
     python tools/trpo_epoch_bench.py --batch_size 2400 --traj_len 120 --reps 3
+    python tools/trpo_epoch_bench.py --hidden_sizes 300 300 300 \
+        --out profiles/trpo_epoch_bench_deep.json
 
 Per epoch, the median [min, max] over --reps epochs after --warmup:
-  sample_kernel   collect_sample_batch on the kernel path (rounds of ops.rollout_goal +
-                  ops.traj_budget);
+  sample_kernel   collect_sample_batch on the kernel path (rounds of ops.rollout_goal, or of
+                  ops.rollout_deep_goal for 3 to 6 hidden layers, + ops.traj_budget);
   sample_host     collect_sample_batch on the reference-shaped host loop in the same process
                   (MEPOL_TRPO_SAMPLER=host): one policy.predict and one env.step per step.  It
                   is the comparison point of the sampler and takes seconds, so it has its own
@@ -19,6 +21,7 @@ Per epoch, the median [min, max] over --reps epochs after --warmup:
                   same process (MEPOL_CRITIC_FIT=host): one torch step per mini-batch.
 Sampling is timed at two policies, since the termination frequency changes the round count: the
 pre-trained-like weights of tests/golden/policy_pretrained_gw.npz and a random initialisation.
+With --hidden_sizes only the random initialisation is timed (the golden weights are [300, 300]).
 The other parts are timed on the random policy's batch.  Wall-clock times between device
 synchronisations: every part ends in a host read or is followed by one.
 """
@@ -34,14 +37,16 @@ GOAL = (5, 5)  # GridGoal1
 GAMMA, LAMBD, KL_THRESH, CG_DAMPING = 0.995, 0.98, 0.001, 0.1
 
 
-def _policies(dev):
+def _policies(dev, hidden=None):
     import numpy as np
     import torch
 
     from mepol_amd.policy import GaussianPolicy
 
     torch.manual_seed(7)
-    random = GaussianPolicy([300, 300], 2, 2, -1.5).to(dev)
+    random = GaussianPolicy(hidden or [300, 300], 2, 2, -1.5).to(dev)
+    if hidden:
+        return {"random": random}
     pre = GaussianPolicy([300, 300], 2, 2, -1.5).to(dev)
     z = np.load(os.path.join(HERE, "tests", "golden", "policy_pretrained_gw.npz"))
     pre.load_state_dict({k[3:]: torch.as_tensor(z[k]) for k in z.files if k.startswith("sd.")})
@@ -71,6 +76,8 @@ def main(argv=None):
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--host_reps", type=int, default=1)
+    p.add_argument("--hidden_sizes", type=int, nargs="+", default=None, metavar="N",
+                   help="hidden widths of the policy; default [300, 300]")
     p.add_argument("--out", default=os.path.join(HERE, "profiles", "trpo_epoch_bench.json"))
     args = p.parse_args(argv)
     sys.path.insert(0, HERE)
@@ -86,7 +93,7 @@ def main(argv=None):
     B, L = args.batch_size, args.traj_len
     rows = {}
     batch = None
-    for name, policy in _policies(dev).items():
+    for name, policy in _policies(dev, args.hidden_sizes).items():
         os.environ["MEPOL_TRPO_SAMPLER"] = "kernel"
         ms, rounds, trajs, dones = [], [], [], []
         for i in range(args.warmup + args.reps):
@@ -113,7 +120,7 @@ def main(argv=None):
         print(json.dumps({k: v for k, v in rows.items() if k.endswith(name)}), flush=True)
 
     # the rest of the epoch on the random policy's last batch
-    policy = _policies(dev)["random"]
+    policy = _policies(dev, args.hidden_sizes)["random"]
     vfunc = create_critic(2).to(device=dev, dtype=torch.float64)
     states, actions, rewards, lens, done = batch
     m, _, nf = states.shape
@@ -148,7 +155,7 @@ def main(argv=None):
     for k in ("critic_fit", "critic_fit_host"):
         rows[k].update(steps=fit_steps, us_per_step=1e3 * rows[k]["median_ms"] / fit_steps)
     rows["critic_fit"]["path"] = "/".join(sorted(fit_paths))
-    result = {"shape": {"batch_size": B, "traj_len": L, "hidden": [300, 300],
+    result = {"shape": {"batch_size": B, "traj_len": L, "hidden": args.hidden_sizes or [300, 300],
                         "cg_iters": args.cg_iters, "kl_thresh": KL_THRESH},
               "run": {"reps": args.reps, "warmup": args.warmup, "host_reps": args.host_reps},
               "device": torch.cuda.get_device_name(0), "rows": rows}

@@ -274,7 +274,9 @@ int mepol_rollout_deep_goal_plan_info(int n_hidden, const int* widths, int a_dim
  * len [n] is below `budget`, and the last one is cut so that the sum equals it.  len_out [n] = the
  * kept lengths (0 for unused trajectories), done_out [n] = done && len_out == len (a cut
  * trajectory is not done), offsets [n+1] int64 = exclusive prefix sum of len_out, meta [2] int64 =
- * {trajectories used, steps kept (< budget when the batch is too short)}.  One workgroup;
+ * {trajectories used, steps kept (< budget when the batch is too short)}.  A negative len counts
+ * as 0; any non-zero done is done, and done_out is 0 or 1.  A trajectory of length 0 that starts
+ * below the budget is used (it counts in meta[0]) and keeps its done.  One workgroup;
  * n > 65536 returns MEPOL_ERR_UNSUPPORTED. */
 int mepol_traj_budget(const int32_t* len, const int32_t* done, int64_t n, int64_t budget,
                       int32_t* len_out, int32_t* done_out, int64_t* offsets, int64_t* meta,
@@ -289,7 +291,12 @@ int mepol_traj_budget(const int32_t* len, const int32_t* done, int64_t n, int64_
  *     c = boot;  t = len-1 .. 0:  c = r_t + gamma c;                       targets = c
  *     A = 0;     t = len-1 .. 0:  A = ((r_t + gamma vn) - values[i][t]) + (gamma lambd) A,
  *                                 vn = t == len-1 ? boot : values[i][t+1];  adv = A
- * Rows whose len / offsets do not fit [0, T] / n_out are skipped (nothing is written for them). */
+ * len and offsets are device data that the host cannot check.  A trajectory is skipped (nothing
+ * is read or written for it) when its len is negative or greater than T, or when its packed rows
+ * [offsets[i], offsets[i] + len[i]) do not lie inside [0, n_out); a len outside [0, T] is never
+ * clamped into it, because offsets was computed for the len that was given.  len = 0 writes
+ * nothing.  The other trajectories of the batch are not affected.  With n_out = 0 nothing is
+ * launched and the four outputs may be null. */
 int mepol_gae(const float* rewards, const double* values, const int32_t* len, const int32_t* done,
               const int64_t* offsets, int64_t n, int64_t T, int64_t n_out, double gamma,
               double lambd, const float* states_rec, int num_features, const float* actions_rec,
@@ -518,7 +525,10 @@ int mepol_mean_tangent(const double* t, const double* z, int64_t n, int hidden, 
  * and no dlog_std): dWm [a_dim, hidden] = c^T relu(z + bz), dbm [a_dim] = column sums of c,
  * dz [n, hidden] (nullable) = (c Wm) * (z + bz > 0), dbz [hidden] (nullable) = column sums of dz.
  * Row sums go through fixed-order partials (the same bits on every call); workspace from
- * mepol_mean_backward_workspace_size.  hidden <= 512, a_dim <= 32. */
+ * mepol_mean_backward_workspace_size.  hidden <= 512, a_dim <= 32.  The outputs are written, not
+ * accumulated, so n <= 0 is refused with MEPOL_ERR_BAD_ARG and nothing is written (as
+ * mepol_head_backward and mepol_layer_backward do); mepol_mean_tangent with n <= 0 succeeds and
+ * writes nothing: it has no output that is a sum over rows. */
 int mepol_mean_backward_workspace_size(int64_t n, int hidden, int a_dim, size_t* bytes);
 int mepol_mean_backward(const double* c, const double* z, int64_t n, int hidden, const double* bz,
                         const double* Wm, int a_dim, double* dz, double* dWm, double* dbm,

@@ -824,8 +824,10 @@ extern "C" int mepol_mean_backward(const double* c, const double* z, int64_t n, 
                                    const double* bz, const double* Wm, int a_dim, double* dz,
                                    double* dWm, double* dbm, double* dbz, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-  if (hidden <= 0 || a_dim <= 0 || !c || !z || !Wm || !dWm || !dbm || !workspace) {
-    set_error("mepol_mean_backward: bad arguments (hidden, a_dim positive; c, z, Wm, dWm, dbm "
+  // n <= 0 is refused, as mepol_head_backward does: the outputs are sums over rows that are
+  // written, not accumulated, and a silent return would leave the caller's bytes in them
+  if (n <= 0 || hidden <= 0 || a_dim <= 0 || !c || !z || !Wm || !dWm || !dbm || !workspace) {
+    set_error("mepol_mean_backward: bad arguments (n, hidden, a_dim positive; c, z, Wm, dWm, dbm "
               "and workspace non-null)");
     return kErrBadArg;
   }
@@ -833,7 +835,6 @@ extern "C" int mepol_mean_backward(const double* c, const double* z, int64_t n, 
     set_error("mepol_mean_backward: hidden <= 512 and action_dim <= 32 only");
     return kErrUnsupported;
   }
-  if (n <= 0) return 0;
   const int nb = grid_mean_bwd(n);
   const size_t need = mean_ws_bytes(n, hidden, a_dim);
   if (workspace_bytes < need) {

@@ -96,10 +96,11 @@ __global__ __launch_bounds__(kWave) void gae_kernel(
     const int64_t i = i0 + lane;
     int l = i < n ? len[i] : 0;
     long long o = i < n ? offsets[i] : 0;
-    // lengths and offsets are device data the host cannot check: nothing outside the inputs'
-    // [.., T] rows is read and nothing outside the n_out packed rows is written
-    l = max(0, (int)min((int64_t)l, T));
-    if (o < 0 || o + l > n_out) l = 0;
+    // lengths and offsets are device data the host cannot check: a row whose len is outside
+    // [0, T] or whose packed rows [o, o + len) do not lie inside [0, n_out) is skipped, so nothing
+    // outside the inputs' [.., T] rows is read and nothing outside the n_out packed rows is
+    // written.  n_out - l cannot overflow (both are in [0, 2^63) by then); o + l could.
+    if (l < 0 || l > T || o < 0 || o > n_out - l) l = 0;
     slen[lane] = l;
     soff[lane] = o;
   }
@@ -241,12 +242,16 @@ extern "C" int mepol_gae(const float* rewards, const double* values, const int32
                          int num_features, const float* actions_rec, int a_dim, double* targets,
                          double* adv, double* states_out, double* actions_out, void* stream) {
   if (n <= 0) return 0;
+  // n_out == 0: there is no packed row to write (the kernel's guard skips every trajectory with
+  // steps), so the outputs may be null then: an empty tensor has no storage
+  const bool outs_ok = n_out == 0 || (targets && adv && states_out && actions_out);
   if (!rewards || !values || !len || !done || !offsets || !states_rec || !actions_rec ||
-      !targets || !adv || !states_out || !actions_out || T <= 0 || T > INT_MAX - 1 ||
-      n_out < 0 || num_features <= 0 || a_dim <= 0 || !(gamma == gamma) || !(lambd == lambd)) {
+      !outs_ok || T <= 0 || T > INT_MAX - 1 || n_out < 0 || num_features <= 0 || a_dim <= 0 ||
+      !(gamma == gamma) || !(lambd == lambd)) {
     set_error("mepol_gae: bad arguments");
     return kErrBadArg;
   }
+  if (n_out == 0) return 0;
   const int64_t blocks = (n + kGaeTraj - 1) / kGaeTraj;
   if (blocks > INT_MAX || num_features > (INT_MAX / kGaeChunk) || a_dim > (INT_MAX / kGaeChunk)) {
     set_error("mepol_gae: batch too large");

@@ -189,6 +189,54 @@ def layer_tangent(x, dW, db, h, out=None):
     return _into(out, np.where(_np(h) > 0.0, _np(x) @ _np(dW).T + _np(db), 0.0))
 
 
+def mean_tangent(t, z, Wm, dWm, dbm, scale, bz=None, out=None):
+    """ops.mean_tangent: scale (t Wm^T + relu(z + bz) dWm^T + dbm); t is not masked."""
+    _, x = _relu_in(z, bz)
+    return _into(out, _np(scale) * (_np(t) @ _np(Wm).T + x @ _np(dWm).T + _np(dbm)))
+
+
+def mean_backward(c, z, Wm, bz=None, need_dz=True, ws=None, dz_out=None, outs=None):
+    """ops.mean_backward: (dz or None, dWm, dbm, dbz or None) from the cotangent c on mu."""
+    pre, x = _relu_in(z, bz)
+    cn = _np(c)
+    if cn.shape[0] == 0:
+        raise ValueError("mean_backward: no rows")
+    dz = np.where(pre > 0.0, cn @ _np(Wm), 0.0)
+    o = outs if outs is not None else (None, None, None)
+    return (_into(dz_out, dz) if need_dz else None, _into(o[0], cn.T @ x),
+            _into(o[1], cn.sum(axis=0)), _into(o[2], dz.sum(axis=0)) if bz is not None else None)
+
+
+# ---------------------------------------------------------------------------------------------
+# TRPO's batch kernels (csrc/trpo_batch.hip) through the sequential restatements of
+# tests/goal_rl_cases.py.
+# ---------------------------------------------------------------------------------------------
+def traj_budget(lens, dones, budget):
+    import goal_rl_cases as C
+
+    lo, do, off, meta = C.budget(_np(lens), _np(dones), int(budget))
+    return (torch.as_tensor(lo), torch.as_tensor(do.astype(np.int32)), torch.as_tensor(off),
+            torch.as_tensor(np.array(meta, dtype=np.int64)))
+
+
+def gae(rewards, values, lens, dones, offsets, n_out, gamma, lambd, states_rec, actions_rec):
+    import goal_rl_cases as C
+
+    nf, a = states_rec.shape[2], actions_rec.shape[2]
+    if int(n_out) == 0:
+        out = (np.zeros(0), np.zeros(0), np.zeros((0, nf)), np.zeros((0, a)))
+    else:
+        out = C.gae_batch(_np(rewards), _np(values), _np(lens), _np(dones), _np(states_rec),
+                          _np(actions_rec), gamma, lambd)
+    return tuple(torch.as_tensor(np.ascontiguousarray(v)) for v in out)
+
+
+def standardize(x, out=None):
+    xn = _np(x).copy()
+    with np.errstate(all="ignore"):
+        return _into(out, (xn - xn.mean()) / xn.std())
+
+
 def optim_step(kind, params, grads, exp_avg, exp_avg_sq, scalars, snapshot=None):
     """csrc/optim.hip's op sequence, one f64 rounding per op, in place; scalars[0] == 0: nothing
     is written.  Snapshots (lists or None) receive the values from before the update."""

@@ -35,9 +35,9 @@ extern "C" {
 /* Bumped on every incompatible change of the signatures below (2: mepol_rollout_mlp takes a
  * workspace; mepol_gemm_dpp removed; 3: mepol_iw_normalize_gathered takes the per-rank
  * trajectory sums).  Additions keep the number: the *_plan_info queries, mepol_critic_fit with
- * mepol_critic_fit_plan_info, and mepol_rollout_deep_goal with
- * mepol_rollout_deep_goal_plan_info, came in at 4.  mepol_abi_version() returns the library's
- * value. */
+ * mepol_critic_fit_plan_info, mepol_rollout_deep_goal with
+ * mepol_rollout_deep_goal_plan_info, and the five mepol_rollout_*goal_threshold* entry points
+ * came in at 4.  mepol_abi_version() returns the library's value. */
 #define MEPOL_ABI_VERSION 4
 
 #define MEPOL_ERR_BAD_ARG 1001
@@ -269,6 +269,51 @@ int mepol_rollout_deep_goal(int env_id, int n_hidden, const int* widths, const d
  * workgroups. */
 int mepol_rollout_deep_goal_plan_info(int n_hidden, const int* widths, int a_dim,
                                       int* resident_workgroups);
+/* Threshold goals, on either env: mepol_rollout_goal's episodes with the hit test of every
+ * non-GridWorld goal of goal_rl.py:91-107 (s[0] >= 7, s[2] >= 3, ...),
+ *     hit <=> (double)state[coord] >= threshold,
+ * where coord is 0 or 1 and state is the env's own state after the step: MountainCar's f64 (p, v)
+ * (env_id 0, init64 [n,2] f64, a_dim = 1) or GridWorld's f32 (sx, sy) widened exactly (env_id 1,
+ * init32 [n,2] f32, a_dim = 2); the other init pointer is not read.  That is what Python computes
+ * for s[coord] >= threshold on the reference's state arrays; a NaN state is no hit.  The hilltop
+ * of MountainCar is coord 0, threshold 0.45: the wall clips p to exactly 0.45 when it is crossed.
+ * Episode results, fully defined outputs, forms, summation order and workspace as for
+ * mepol_rollout_goal: up to the end of each episode the recorded states and actions are the bits
+ * mepol_rollout_mlp records.  MEPOL_ERR_BAD_ARG, before any launch, for coord outside {0, 1}, a
+ * NaN threshold (+-inf are legal: never / always a hit), env_id outside {0, 1}, a_dim != 1 for
+ * env 0 or != 2 for env 1, the null init pointer of the chosen env, a null output, and a shape
+ * outside mepol_rollout_mlp's (hidden <= 512); n <= 0 or T <= 0 returns 0 without a launch. */
+int mepol_rollout_goal_threshold(int env_id, const double* W1, const double* b1, int h0,
+                                 const double* W2t, const double* b2, int h1, const double* Wm,
+                                 const double* bm, const double* log_std, int a_dim,
+                                 const double* init64, const float* init32, const double* noise,
+                                 int64_t n, int64_t T, int coord, double threshold,
+                                 float* states_rec, float* actions_rec, float* rewards_rec,
+                                 int32_t* len_out, int32_t* done_out, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+/* Workspace and form of mepol_rollout_goal_threshold: as mepol_rollout_goal_workspace_size and
+ * mepol_rollout_goal_plan_info, by the occupancy of the instance that runs (env x threshold). */
+int mepol_rollout_goal_threshold_workspace_size(int env_id, int64_t n, int64_t T, int h0, int h1,
+                                                int a_dim, size_t* bytes);
+int mepol_rollout_goal_threshold_plan_info(int env_id, int64_t n, int h0, int h1, int a_dim,
+                                           int* workgroups_per_traj, int* k_chunks);
+/* mepol_rollout_goal_threshold for the policies of mepol_rollout_deep (3 <= n_hidden <= 6): the
+ * same hit test, episode results and argument checks (shapes: mepol_rollout_deep's), and up to
+ * the end of each episode the recorded states and actions are the bits mepol_rollout_deep
+ * records.  One workgroup per trajectory; the workspace (nullable) is
+ * mepol_rollout_deep_workspace_size's (MEPOL_ERR_WORKSPACE if smaller). */
+int mepol_rollout_deep_goal_threshold(int env_id, int n_hidden, const int* widths,
+                                      const double* W1, const double* b1, const double* Wt,
+                                      const double* bt, const double* Wm, const double* bm,
+                                      const double* log_std, int a_dim, const double* init64,
+                                      const float* init32, const double* noise, int64_t n,
+                                      int64_t T, int coord, double threshold, float* states_rec,
+                                      float* actions_rec, float* rewards_rec, int32_t* len_out,
+                                      int32_t* done_out, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+/* mepol_rollout_deep_goal_plan_info for the threshold instance of this env. */
+int mepol_rollout_deep_goal_threshold_plan_info(int env_id, int n_hidden, const int* widths,
+                                                int a_dim, int* resident_workgroups);
 /* The step budget of collect_sample_batch (`steps == batch_size`, trpo.py:98-140) over a batch
  * that was rolled out in parallel: trajectories are taken in index order while the running sum of
  * len [n] is below `budget`, and the last one is cut so that the sum equals it.  len_out [n] = the

@@ -127,6 +127,20 @@ SIGNATURES = {
                                 _c_vp, _c_vp, _c_sz, _c_vp],
     "mepol_rollout_deep_goal_plan_info": [_c_int, ctypes.POINTER(_c_int), _c_int,
                                           ctypes.POINTER(_c_int)],
+    "mepol_rollout_goal_threshold": [_c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp,
+                                     _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64,
+                                     _c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                     _c_sz, _c_vp],
+    "mepol_rollout_goal_threshold_workspace_size": [_c_int, _c_i64, _c_i64, _c_int, _c_int, _c_int,
+                                                    ctypes.POINTER(_c_sz)],
+    "mepol_rollout_goal_threshold_plan_info": [_c_int, _c_i64, _c_int, _c_int, _c_int,
+                                               ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)],
+    "mepol_rollout_deep_goal_threshold": [_c_int, _c_int, ctypes.POINTER(_c_int), _c_vp, _c_vp,
+                                          _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
+                                          _c_vp, _c_i64, _c_i64, _c_int, _c_dbl, _c_vp, _c_vp,
+                                          _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp],
+    "mepol_rollout_deep_goal_threshold_plan_info": [_c_int, _c_int, ctypes.POINTER(_c_int), _c_int,
+                                                    ctypes.POINTER(_c_int)],
     "mepol_traj_budget": [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],
     "mepol_gae": [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_dbl, _c_dbl, _c_vp,
                   _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],

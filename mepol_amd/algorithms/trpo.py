@@ -25,11 +25,13 @@ F.linear restatement of mu (it must not go through policy._Linear, whose weight 
 kernel call without an autograd graph behind it).
 
 Sampling and batch processing ("TRPO sampling and batch processing").  The reference
-steps one env at a time through policy.predict.  For a GridWorld goal env and a ReLU policy with
-two to six hidden layers (kernel_path.goal_sampler) collect_sample_batch rolls whole rounds of
-trajectories out in one launch each (ops.rollout_goal for two layers, ops.rollout_deep_goal for
-three to six: termination and the sparse reward inside the kernel), applies the reference's step
-budget on the device (ops.traj_budget) and reads two or three words per round;
+steps one env at a time through policy.predict.  For a GridWorld or MountainCar goal env and a
+ReLU policy with two to six hidden layers (kernel_path.goal_sampler) collect_sample_batch rolls
+whole rounds of trajectories out in one launch each (ops.rollout_goal for two layers,
+ops.rollout_deep_goal for three to six: termination and the sparse reward inside the kernel; for
+a threshold goal, on GridWorld or MountainCar, ops.rollout_goal_threshold and
+ops.rollout_deep_goal_threshold), applies the reference's step budget on the device
+(ops.traj_budget) and reads two or three words per round;
 process_batch computes targets, GAE advantages and the packed batch with ops.gae and
 ops.standardize.  Every other env, policy or device takes the reference's sequential loop, and
 CPU tensors a numpy restatement of the same arithmetic.
@@ -54,7 +56,7 @@ import torch.nn.functional as F
 
 from .. import kernel_path, ops
 from .. import policy as _policy
-from ..envs.wrappers import unwrap
+from ..envs.wrappers import ThresholdGoal, unwrap
 from ..kernel_path import linear_layers
 
 KL_VAR_EPS = 1e-7  # the epsilon on the variance in the reference's KL (trpo.py:384)
@@ -371,15 +373,23 @@ ROUND_MAX_TRAJ = 65536  # mepol_traj_budget's limit
 _ROUND_CAPACITY = {}
 
 
-def _round_capacity(h0, h1, a_dim, device):
-    """Trajectories per round that cost no more time than one: the most for which
-    ops.rollout_goal_plan (the goal kernel's own occupancy) still reports the multi-workgroup
-    form, found once per shape and MEPOL_ROLLOUT_MW setting by bisection, or, where there is no
-    such form, one workgroup per CU."""
-    key = (h0, h1, a_dim, device, os.environ.get("MEPOL_ROLLOUT_MW"))
+BALL, THRESHOLD = "ball", "threshold"  # the goal kinds of the rollout kernels
+MOUNTAINCAR, GRIDWORLD = 0, 1          # their env_id
+
+
+def _round_capacity(h0, h1, a_dim, device, env_id=GRIDWORLD, kind=BALL):
+    """Trajectories per round that cost no more time than one: the most for which the plan of
+    the instance that runs (ops.rollout_goal_plan for GridWorld's ball goal,
+    ops.rollout_goal_threshold_plan for a threshold goal on env_id: each kernel's own occupancy)
+    still reports the multi-workgroup form, found once per shape, env, goal kind and
+    MEPOL_ROLLOUT_MW setting by bisection, or, where there is no such form, one workgroup per
+    CU."""
+    key = (h0, h1, a_dim, device, os.environ.get("MEPOL_ROLLOUT_MW"), env_id, kind)
     if key not in _ROUND_CAPACITY:
         def multi(n):
-            return ops.rollout_goal_plan(n, h0, h1, a_dim)["workgroups_per_traj"] > 1
+            plan = (ops.rollout_goal_plan(n, h0, h1, a_dim) if kind == BALL
+                    else ops.rollout_goal_threshold_plan(env_id, n, h0, h1, a_dim))
+            return plan["workgroups_per_traj"] > 1
 
         lo, hi = 0, 1 << 16  # multi(n) holds up to some n < hi (no device holds 65,536 parts)
         while lo + 1 < hi:
@@ -389,19 +399,23 @@ def _round_capacity(h0, h1, a_dim, device):
     return _ROUND_CAPACITY[key]
 
 
-def _round_capacity_deep(widths, a_dim, device):
+def _round_capacity_deep(widths, a_dim, device, env_id=GRIDWORLD, kind=BALL):
     """_round_capacity for a policy with 3 to 6 hidden layers: the trajectories (one workgroup
-    each) the device holds at once (ops.rollout_deep_goal_plan), found once per shape and
-    MEPOL_ROLLOUT_KL setting (the resident rows set the kernel's LDS, so its occupancy)."""
-    key = (tuple(widths), a_dim, device, os.environ.get("MEPOL_ROLLOUT_KL"))
+    each) the device holds at once (ops.rollout_deep_goal_plan, or
+    ops.rollout_deep_goal_threshold_plan for a threshold goal on env_id), found once per shape,
+    env, goal kind and MEPOL_ROLLOUT_KL setting (the resident rows set the kernel's LDS, so its
+    occupancy)."""
+    key = (tuple(widths), a_dim, device, os.environ.get("MEPOL_ROLLOUT_KL"), env_id, kind)
     if key not in _ROUND_CAPACITY:
-        plan = ops.rollout_deep_goal_plan(widths, a_dim)
+        plan = (ops.rollout_deep_goal_plan(widths, a_dim) if kind == BALL
+                else ops.rollout_deep_goal_threshold_plan(env_id, widths, a_dim))
         _ROUND_CAPACITY[key] = max(plan["resident_workgroups"], 1)
     return _ROUND_CAPACITY[key]
 
 
 def _draw_round(base, R, T, a_dim, device, generator):
-    """Initial states f32 [R, 2] and action noise f64 [T, R, a] of one round, in this order."""
+    """Initial states [R, 2] in the env's own dtype (GridWorld f32, MountainCar f64) and action
+    noise f64 [T, R, a] of one round, in this order."""
     init = base.reset_batch_torch(R, device, generator)
     noise = torch.randn((T, R, a_dim), dtype=torch.float64, device=device, generator=generator)
     return init, noise
@@ -411,11 +425,14 @@ def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, r
     dev = policy.device
     base = unwrap(env)
     a_dim = policy.action_dim
-    deep = len(layers) > 2  # ops.rollout_deep_goal: no error word, so no re-run
+    deep = len(layers) > 2  # the deep rollouts have no error word, so no re-run
+    # the kernel instance: env x goal kind (kernel_path.goal_sampler admits no other pair)
+    env_id = MOUNTAINCAR if type(base).batched_kind == "mountaincar" else GRIDWORLD
+    kind = THRESHOLD if isinstance(goal, ThresholdGoal) else BALL
     widths = [W.shape[0] for W, _ in layers]
     head = (policy.mean.weight.detach(), policy.mean.bias.detach(), policy.log_std.detach())
-    cap = (_round_capacity_deep(widths, a_dim, dev) if deep
-           else _round_capacity(*widths, a_dim, dev))
+    cap = (_round_capacity_deep(widths, a_dim, dev, env_id, kind) if deep
+           else _round_capacity(*widths, a_dim, dev, env_id, kind))
     steps_idx = torch.arange(T + 1, device=dev)
     remaining, rounds, parts = int(batch_size), 0, []
     while remaining > 0:
@@ -428,16 +445,25 @@ def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, r
         rewards = torch.empty((R, T), dtype=torch.float32, device=dev)
         lens = torch.empty(R, dtype=torch.int32, device=dev)
         dones = torch.empty(R, dtype=torch.int32, device=dev)
-        roll = (*head, init.to(torch.float32), noise, goal.goal, goal.radius, states, actions,
-                rewards, lens, dones)
+        if env_id == GRIDWORLD:
+            init = init.to(torch.float32)
+        test = (goal.goal, goal.radius) if kind == BALL else (goal.index, goal.threshold)
+        roll = (*head, init, noise, *test, states, actions, rewards, lens, dones)
         if deep:
-            ops.rollout_deep_goal(layers, *roll)
+            if kind == BALL:
+                ops.rollout_deep_goal(layers, *roll)
+            else:
+                ops.rollout_deep_goal_threshold(env_id, layers, *roll)
             kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
             # the round's one host synchronisation: {trajectories used, steps kept}
             m, kept = meta.tolist()
         else:
             (W1, b1), (W2, b2) = layers
-            err, rerun = ops.rollout_goal(W1, b1, W2, b2, *roll, defer_check=True)
+            if kind == BALL:
+                err, rerun = ops.rollout_goal(W1, b1, W2, b2, *roll, defer_check=True)
+            else:
+                err, rerun = ops.rollout_goal_threshold(env_id, W1, b1, W2, b2, *roll,
+                                                        defer_check=True)
             kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
             # the round's one host synchronisation: {trajectories used, steps kept, error word}
             m, kept, bad = torch.cat([meta, err.to(torch.int64)]).tolist()
@@ -504,9 +530,9 @@ def collect_sample_batch(env, policy, batch_size, traj_len, num_workers=1, gener
     (DESIGN.md).  R = round_traj, or the larger of ceil(remaining / traj_len) and the most
     trajectories the multi-workgroup rollout holds (_round_capacity; for 3 to 6 hidden layers
     the workgroups the device holds at once, _round_capacity_deep).  `generator` seeds the
-    draws; `draw(R, T, a, device) -> (init f32 [R, 2], noise f64 [T, R, a])` replaces them
-    (tests).  num_workers is ignored there.  Everything else runs the reference's sequential
-    loop with one worker."""
+    draws; `draw(R, T, a, device) -> (init [R, 2] in the env's dtype, GridWorld f32 / MountainCar
+    f64, noise f64 [T, R, a])` replaces them (tests).  num_workers is ignored there.  Everything
+    else runs the reference's sequential loop with one worker."""
     if not hasattr(env.action_space, "shape") or hasattr(env.action_space, "n"):
         raise NotImplementedError("collect_sample_batch: continuous action spaces only")
     spec = kernel_path.goal_sampler(env, policy)

@@ -101,8 +101,9 @@ constexpr unsigned long long kMailEmpty = ~0ull;
 constexpr int kRollMaxA = 8;
 constexpr int kRollChunks = 4;
 
-// Goal mode (GOAL = true, GridWorld only): GoalArgs, goal_hit and goal_zero_tail of goal_mode.hpp.
-template <int ENV, int U, bool GOAL = false>
+// Goal mode (GOAL = kGoalBall, GridWorld only, or kGoalThreshold, either env): GoalArgs, goal_test
+// and goal_zero_tail of goal_mode.hpp.
+template <int ENV, int U, int GOAL = kGoalNone>
 __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, int h0,
     const double* __restrict__ W2t, const double* __restrict__ b2, int h1,
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     const float* __restrict__ init32, const double* __restrict__ noise, int64_t n, int64_t T,
     float* __restrict__ states_rec, float* __restrict__ actions_rec,
     double* __restrict__ visited, double* __restrict__ final_state, int KL, GoalArgs goal) {
-  static_assert(!GOAL || ENV == 1, "goal mode is GridWorld's");
+  static_assert(GOAL != kGoalBall || ENV == 1, "the ball goal is GridWorld's");
   extern __shared__ double sW2[];  // [KL][blockDim.x]: W2^T rows 0 .. KL - 1
   __shared__ double sx[2];
   __shared__ int sgoal;  // GOAL: the step just taken reached the goal (thread 0 writes it)
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     }
     states_rec[(i * (T + 1)) * 2 + 0] = (float)sx[0];
     states_rec[(i * (T + 1)) * 2 + 1] = (float)sx[1];
-    if constexpr (GOAL) sgoal = 0;
+    if constexpr (GOAL != kGoalNone) sgoal = 0;
   }
   int64_t steps = T;  // GOAL: the episode's length
   // thread 0: exp(log_std) once, and the next step's noise loaded a step ahead (its global
@@ -232,14 +233,14 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
         visited[(i * T + t) * 2 + 0] = sx[0];
         visited[(i * T + t) * 2 + 1] = sx[1];
       }
-      if constexpr (GOAL) {
-        const bool hit = goal_hit(gx, gy, goal);
+      if constexpr (GOAL != kGoalNone) {
+        const bool hit = goal_test<GOAL, ENV>(p, v, gx, gy, goal);
         goal.rewards[i * T + t] = hit ? 1.f : 0.f;
         if (hit) sgoal = 1;
       }
     }
     __syncthreads();
-    if constexpr (GOAL) {
+    if constexpr (GOAL != kGoalNone) {
       if (sgoal) {  // workgroup-uniform: written before the barrier, never cleared
         steps = t + 1;
         break;
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     final_state[2 * i] = sx[0];
     final_state[2 * i + 1] = sx[1];
   }
-  if constexpr (GOAL) {
+  if constexpr (GOAL != kGoalNone) {
     if (j == 0) {
       goal.len[i] = (int)steps;
       goal.done[i] = sgoal;
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
 // PROBE (tools/variants/rollout_probe.hip only): thread 0 of each workgroup accumulates
 // s_memtime spans of the step's phases into probe[blockIdx.x][8]; the product has PROBE = false.
 constexpr int kRollMwWaves = kRollChunks;  // one layer-2 chain per wave
-template <int ENV, bool PROBE = false, bool GOAL = false>
+template <int ENV, bool PROBE = false, int GOAL = kGoalNone>
 __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, int h0,
     const double* __restrict__ W2t, const double* __restrict__ b2, int h1,
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     double* __restrict__ visited, double* __restrict__ final_state, int np, int nw,
     unsigned long long* __restrict__ mail, int* __restrict__ err, int* __restrict__ ticket,
     long long* __restrict__ probe, GoalArgs goal) {
-  static_assert(!GOAL || ENV == 1, "goal mode is GridWorld's");
+  static_assert(GOAL != kGoalBall || ENV == 1, "the ball goal is GridWorld's");
   extern __shared__ double sW2[];  // [h0][64]: W2^T rows, this part's 64 columns
   __shared__ double sh1[kRollMaxH];
   __shared__ double spart[kRollMwWaves][64];
@@ -318,6 +319,14 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
   // and read every part's word of step t (it needs them for the action that caused the hit), so
   // no peer ever waits for a word that will not be written; leaving early only frees its slot
   // sooner for the tickets behind it.
+  // That rests on every part taking the `break` at the same step: a part that left a step
+  // before its peers would leave them polling a word it never writes, which is a hang (bounded
+  // by the spin limit: err = 1), not a wrong number.  It holds for both envs and both goal
+  // kinds because every thread of every part computes the hit itself, from its own copy of the
+  // state (pp, vv) / (gx, gy), never from a flag another part wrote, and the copies are the same
+  // bits: each is stepped by the same instruction sequence (MountainCar::step, its cos()
+  // included, or GridWorld::step) on the same action, the part-ordered sum of the same mail
+  // words.  Keep the env step and the hit test free of anything that differs between parts.
   __shared__ int sticket;
   if (threadIdx.x == 0) sticket = atomicAdd(ticket, 1);
   __syncthreads();
@@ -519,8 +528,9 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
       }
     }
     stamp(4, x0);
-    if constexpr (GOAL) {
-      hit = goal_hit(gx, gy, goal);  // the same value in every thread of every part
+    if constexpr (GOAL != kGoalNone) {
+      // the same value in every thread of every part
+      hit = goal_test<GOAL, ENV>(pp, vv, gx, gy, goal);
       if (rec) goal.rewards[i * T + t] = hit ? 1.f : 0.f;
       if (hit) {
         steps = t + 1;
@@ -532,7 +542,7 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     final_state[2 * i] = x0;
     final_state[2 * i + 1] = x1;
   }
-  if constexpr (GOAL) {
+  if constexpr (GOAL != kGoalNone) {
     if (rec) {
       goal.len[i] = (int)steps;
       goal.done[i] = hit ? 1 : 0;
@@ -611,11 +621,25 @@ static size_t rollout_mw_bytes(int64_t n, int64_t T, int h1, int a_dim) {
 // [h0][64] f64 slice (dynamic) + sh1, spart, sword (static, 6.5 KB) within 160 KB of LDS
 static constexpr int kRollMwMaxH0 = 306;
 
-template <int ENV, bool GOAL = false>
+template <int ENV, int GOAL = kGoalNone>
 static int rollout_mw_prepare() {
   MEPOL_HIP((max_dynamic_lds<rollout_mlp_mw_kernel<ENV, false, GOAL>>(
       kRollMwMaxH0 * 64 * (int)sizeof(double))));
   return 0;
+}
+
+// Workgroups of the <ENV, GOAL> instance a CU holds at this dynamic LDS size; 0 on any error.
+template <int ENV, int GOAL>
+static int rollout_mw_per_cu(size_t lds) {
+  int per_cu = 0;
+  if (rollout_mw_prepare<ENV, GOAL>()) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &per_cu, rollout_mlp_mw_kernel<ENV, false, GOAL>, 64 * kRollMwWaves, lds) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return per_cu;
 }
 
 // The multi-workgroup form's parts exchange partial sums every step.  Its workgroups take
@@ -627,7 +651,10 @@ static int rollout_mw_prepare() {
 // dedicated queue crashed the process at exit under rocprofv3: HIP's teardown of that queue
 // faulted inside libhsa-runtime64 after the profiler had shut its queue interception down,
 // profiles/r5/rollout_exit_crash.txt.)
-static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim, bool goal = false) {
+// The occupancy asked is that of the instance that will run, env x goal kind: each has its own
+// register count.
+static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim,
+                          int goal = kGoalNone) {
   const int np = (h1 + 63) / 64;
   const char* mw = getenv("MEPOL_ROLLOUT_MW");
   if (h0 > kRollMwMaxH0 || np * a_dim > 64 || (mw && mw[0] == '0')) return 0;
@@ -636,26 +663,16 @@ static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim, bool
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return 0;
   const size_t lds = (size_t)h0 * 64 * sizeof(double);
-  int per_cu = 0;
-  hipError_t e;
-  if (goal) {  // the goal-mode instance's own resources (env 1 only)
-    if (rollout_mw_prepare<1, true>()) return 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, rollout_mlp_mw_kernel<1, false, true>, 64 * kRollMwWaves, lds);
-  } else if (env_id == 0) {
-    if (rollout_mw_prepare<0>()) return 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_mlp_mw_kernel<0>,
-                                                     64 * kRollMwWaves, lds);
-  } else {
-    if (rollout_mw_prepare<1>()) return 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_mlp_mw_kernel<1>,
-                                                     64 * kRollMwWaves, lds);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return n * np <= (int64_t)per_cu * cus;
+  int per_cu;
+  if (goal == kGoalBall)  // (env 1 only)
+    per_cu = rollout_mw_per_cu<1, kGoalBall>(lds);
+  else if (goal == kGoalThreshold)
+    per_cu = env_id == 0 ? rollout_mw_per_cu<0, kGoalThreshold>(lds)
+                         : rollout_mw_per_cu<1, kGoalThreshold>(lds);
+  else
+    per_cu = env_id == 0 ? rollout_mw_per_cu<0, kGoalNone>(lds)
+                         : rollout_mw_per_cu<1, kGoalNone>(lds);
+  return per_cu > 0 && n * np <= (int64_t)per_cu * cus;
 }
 
 extern "C" int mepol_rollout_mlp_plan_info(int64_t n, int h0, int h1, int a_dim,
@@ -684,7 +701,7 @@ extern "C" int mepol_rollout_mlp_workspace_size(int64_t n, int64_t T, int h0, in
   return 0;
 }
 
-template <int ENV, bool GOAL = false>
+template <int ENV, int GOAL = kGoalNone>
 static hipError_t rollout_mw_launch(const double* W1, const double* b1, int h0,
                                     const double* W2t, const double* b2, int h1, const double* Wm,
                                     const double* bm, const double* log_std, int a_dim,
@@ -711,23 +728,25 @@ extern "C" int mepol_rollout_goal_plan_info(int64_t n, int h0, int h1, int a_dim
     set_error("mepol_rollout_goal_plan_info: bad arguments");
     return kErrBadArg;
   }
-  const int mw = rollout_use_mw(1, n, h0, h1, a_dim, true);
+  const int mw = rollout_use_mw(1, n, h0, h1, a_dim, kGoalBall);
   *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
   *k_chunks = kRollChunks;  // both forms
   return 0;
 }
 
-// mepol_rollout_mlp (goal == nullptr) and mepol_rollout_goal (env 1) behind their argument
-// checks: the same choice of form, workspace layout and launches, the kernels' GOAL instances
-// for the second.
+// mepol_rollout_mlp (goal == nullptr), mepol_rollout_goal (kind kGoalBall, env 1) and
+// mepol_rollout_goal_threshold (kind kGoalThreshold) behind their argument checks: the same
+// choice of form, workspace layout and launches, the kernels' GOAL instances for the last two.
 static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h0,
                            const double* W2t, const double* b2, int h1, const double* Wm,
                            const double* bm, const double* log_std, int a_dim,
                            const double* init64, const float* init32, const double* noise,
                            int64_t n, int64_t T, float* states_rec, float* actions_rec,
                            double* visited, double* final_state, const GoalArgs* goal,
-                           void* workspace, size_t workspace_bytes, void* stream) {
+                           void* workspace, size_t workspace_bytes, void* stream,
+                           int kind = kGoalBall) {
   const GoalArgs ga = goal ? *goal : GoalArgs{};
+  if (!goal) kind = kGoalNone;
   const int threads = ((h0 > h1 ? h0 : h1) + 63) / 64 * 64;
   hipStream_t st = (hipStream_t)stream;
   int* err = (int*)workspace;
@@ -736,7 +755,7 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
     // several workgroups per trajectory when all of them can be resident at once
     const int np = (h1 + 63) / 64, nw = threads / 64;
     if (workspace && workspace_bytes >= rollout_mw_bytes(n, T, h1, a_dim) &&
-        rollout_use_mw(env_id, n, h0, h1, a_dim, goal != nullptr)) {
+        rollout_use_mw(env_id, n, h0, h1, a_dim, kind)) {
       unsigned long long* mail = (unsigned long long*)((char*)workspace + 256);
       int* ticket = err + 1;  // word 1 of the 256-byte header: the dispatch-order counter
       MEPOL_HIP(hipMemsetAsync(ticket, 0, sizeof(int), st));
@@ -746,9 +765,11 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
   rollout_mw_launch<E, G>(W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, \
                           n, T, states_rec, actions_rec, visited, final_state, np, nw, mail, err, \
                           ticket, ga, st)
-      const hipError_t e = goal          ? MEPOL_ROLL_MW(1, true)
-                           : env_id == 0 ? MEPOL_ROLL_MW(0, false)
-                                         : MEPOL_ROLL_MW(1, false);
+      const hipError_t e =
+          kind == kGoalBall ? MEPOL_ROLL_MW(1, kGoalBall)
+          : kind == kGoalThreshold
+              ? (env_id == 0 ? MEPOL_ROLL_MW(0, kGoalThreshold) : MEPOL_ROLL_MW(1, kGoalThreshold))
+              : (env_id == 0 ? MEPOL_ROLL_MW(0, kGoalNone) : MEPOL_ROLL_MW(1, kGoalNone));
 #undef MEPOL_ROLL_MW
       if (e == hipSuccess) return 0;
       (void)hipGetLastError();  // launch refused: the one-workgroup form
@@ -768,12 +789,16 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
                        b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T, states_rec,   \
                        actions_rec, visited, final_state, KL, ga);                                \
   } while (0)
-  if (goal)
-    MEPOL_ROLL(1, 8, true);
+  if (kind == kGoalBall)
+    MEPOL_ROLL(1, 8, kGoalBall);
+  else if (kind == kGoalThreshold && env_id == 0)
+    MEPOL_ROLL(0, 8, kGoalThreshold);
+  else if (kind == kGoalThreshold)
+    MEPOL_ROLL(1, 8, kGoalThreshold);
   else if (env_id == 0)
-    MEPOL_ROLL(0, 8, false);
+    MEPOL_ROLL(0, 8, kGoalNone);
   else
-    MEPOL_ROLL(1, 8, false);
+    MEPOL_ROLL(1, 8, kGoalNone);
 #undef MEPOL_ROLL
   MEPOL_CHECK_LAUNCH();
   return 0;
@@ -814,8 +839,9 @@ extern "C" int mepol_rollout_goal_workspace_size(int env_id, int64_t n, int64_t 
     set_error("mepol_rollout_goal: only GridWorld (env_id 1) has a goal mode");
     return kErrUnsupported;
   }
-  *bytes = (n > 0 && rollout_use_mw(1, n, h0, h1, a_dim, true)) ? rollout_mw_bytes(n, T, h1, a_dim)
-                                                                : 256;
+  *bytes = (n > 0 && rollout_use_mw(1, n, h0, h1, a_dim, kGoalBall))
+               ? rollout_mw_bytes(n, T, h1, a_dim)
+               : 256;
   return 0;
 }
 
@@ -841,8 +867,67 @@ extern "C" int mepol_rollout_goal(int env_id, const double* W1, const double* b1
     set_error("mepol_rollout_goal: only GridWorld (env_id 1) has a goal mode");
     return kErrUnsupported;
   }
-  const GoalArgs goal{goal_x, goal_y, radius, rewards_rec, len_out, done_out};
+  const GoalArgs goal{{goal_x}, goal_y, {radius}, rewards_rec, len_out, done_out};
   return rollout_mlp_run(1, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, nullptr, init32,
                          noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
                          workspace_bytes, stream);
+}
+
+// ---- threshold goals (either env) -------------------------------------------------------------
+// The shape and env checks the three mepol_rollout_goal_threshold* entry points share: the limits
+// of mepol_rollout_mlp, and the env's own action count.
+static bool threshold_shape_ok(int env_id, int h0, int h1, int a_dim) {
+  return env_id >= 0 && env_id <= 1 && h0 > 0 && h1 > 0 && h0 <= kRollMaxH && h1 <= kRollMaxH &&
+         a_dim == (env_id == 0 ? 1 : 2);
+}
+
+extern "C" int mepol_rollout_goal_threshold_plan_info(int env_id, int64_t n, int h0, int h1,
+                                                      int a_dim, int* workgroups_per_traj,
+                                                      int* k_chunks) {
+  if (n <= 0 || !threshold_shape_ok(env_id, h0, h1, a_dim) || !workgroups_per_traj || !k_chunks) {
+    set_error("mepol_rollout_goal_threshold_plan_info: bad arguments (env 0 with a_dim = 1 or "
+              "env 1 with a_dim = 2, hidden <= %d)", kRollMaxH);
+    return kErrBadArg;
+  }
+  const int mw = rollout_use_mw(env_id, n, h0, h1, a_dim, kGoalThreshold);
+  *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
+  *k_chunks = kRollChunks;  // both forms
+  return 0;
+}
+
+extern "C" int mepol_rollout_goal_threshold_workspace_size(int env_id, int64_t n, int64_t T,
+                                                           int h0, int h1, int a_dim,
+                                                           size_t* bytes) {
+  if (n < 0 || T < 0 || !threshold_shape_ok(env_id, h0, h1, a_dim) || !bytes) {
+    set_error("mepol_rollout_goal_threshold_workspace_size: bad arguments (env 0 with a_dim = 1 "
+              "or env 1 with a_dim = 2, hidden <= %d)", kRollMaxH);
+    return kErrBadArg;
+  }
+  *bytes = (n > 0 && rollout_use_mw(env_id, n, h0, h1, a_dim, kGoalThreshold))
+               ? rollout_mw_bytes(n, T, h1, a_dim)
+               : 256;
+  return 0;
+}
+
+extern "C" int mepol_rollout_goal_threshold(
+    int env_id, const double* W1, const double* b1, int h0, const double* W2t, const double* b2,
+    int h1, const double* Wm, const double* bm, const double* log_std, int a_dim,
+    const double* init64, const float* init32, const double* noise, int64_t n, int64_t T,
+    int coord, double threshold, float* states_rec, float* actions_rec, float* rewards_rec,
+    int32_t* len_out, int32_t* done_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n <= 0 || T <= 0) return 0;
+  if (!threshold_shape_ok(env_id, h0, h1, a_dim) || T > INT32_MAX || (env_id == 0 && !init64) ||
+      (env_id == 1 && !init32) || !W1 || !b1 || !W2t || !b2 || !Wm || !bm || !log_std || !noise ||
+      !states_rec || !actions_rec || !rewards_rec || !len_out || !done_out ||
+      (coord != 0 && coord != 1) || threshold != threshold ||
+      (workspace && workspace_bytes < sizeof(int))) {
+    set_error("mepol_rollout_goal_threshold: bad arguments (env 0 with a_dim = 1 and init64 or "
+              "env 1 with a_dim = 2 and init32, hidden <= %d, coord 0 or 1, threshold not NaN, "
+              "no null pointers)", kRollMaxH);
+    return kErrBadArg;
+  }
+  const GoalArgs goal = threshold_goal(coord, threshold, rewards_rec, len_out, done_out);
+  return rollout_mlp_run(env_id, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32,
+                         noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
+                         workspace_bytes, stream, kGoalThreshold);
 }

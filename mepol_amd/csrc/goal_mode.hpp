@@ -1,22 +1,49 @@
-// Goal mode of the one-launch rollouts (GOAL = true, GridWorld only), shared by the two-layer
-// kernels (envs.hip) and the deep one (rollout_deep.hip): the sparse-reward episodes of
-// goal_rl.py:61-77 under CustomRewardEnv (wrappers.py:40-52).  After each env step the f32 state is
-// tested against the goal; a hit at step t gives rewards[i, t] = 1, len[i] = t + 1, done[i] = 1,
-// s_{t+1} is recorded and the trajectory's workgroup(s) leave.  Every output row past the end is
-// written as zeros, so the caller's buffers need no clearing.  GOAL = false never reads GoalArgs.
+// Goal mode of the one-launch rollouts, shared by the two-layer kernels (envs.hip) and the deep one
+// (rollout_deep.hip): the sparse-reward episodes of goal_rl.py:61-107 under CustomRewardEnv
+// (wrappers.py:40-52).  The kernels' GOAL template argument names the kind of goal, so that each
+// instance holds one hit test and no run-time choice between them:
+//   kGoalNone       no goal mode (GoalArgs is never read);
+//   kGoalBall       GridWorld only: the f32 state within `radius` of the f32 goal (goal_hit);
+//   kGoalThreshold  either env: state[coord] >= threshold on the env's own state, MountainCar's
+//                   f64 (p, v) or GridWorld's f32 (sx, sy) widened exactly (goal_hit_threshold).
+// After each env step the state is tested; a hit at step t gives rewards[i, t] = 1,
+// len[i] = t + 1, done[i] = 1, s_{t+1} is recorded and the trajectory's workgroup(s) leave.  Every
+// output row past the end is written as zeros, so the caller's buffers need no clearing.
 #pragma once
 #include "common.hpp"
 
 namespace mepol {
 namespace envs {
 
+constexpr int kGoalNone = 0, kGoalBall = 1, kGoalThreshold = 2;
+
+// One layout for both kinds (the threshold's two values share the ball's words), so that the
+// kernels' argument blocks, and with them the ball instances' code, are what they were before the
+// threshold kind existed.
 struct GoalArgs {
-  float x, y;      // the goal
-  double radius;
+  union {
+    float x;    // kGoalBall: the goal, with y
+    int coord;  // kGoalThreshold: the state coordinate tested, 0 or 1
+  };
+  float y;
+  union {
+    double radius;     // kGoalBall
+    double threshold;  // kGoalThreshold
+  };
   float* rewards;  // [n, T]
   int* len;        // [n]
   int* done;       // [n]
 };
+
+inline GoalArgs threshold_goal(int coord, double threshold, float* rewards, int* len, int* done) {
+  GoalArgs g{};
+  g.coord = coord;
+  g.threshold = threshold;
+  g.rewards = rewards;
+  g.len = len;
+  g.done = done;
+  return g;
+}
 
 // np.linalg.norm(s - goal) <= radius with an f32 state and goal and a Python-float radius
 // (numpy 1.x: the f32 norm is widened for the comparison): every operation rounded on its own.
@@ -24,6 +51,26 @@ __device__ __forceinline__ bool goal_hit(float sx, float sy, const GoalArgs& g) 
   const float dx = __fsub_rn(sx, g.x), dy = __fsub_rn(sy, g.y);
   const float q = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
   return (double)__fsqrt_rn(q) <= g.radius;
+}
+
+// s[coord] >= threshold as Python compares a state array's element with a float: in f64, and a
+// NaN state is no hit (an ordered compare).
+__device__ __forceinline__ bool goal_hit_threshold(double s0, double s1, const GoalArgs& g) {
+  return (g.coord ? s1 : s0) >= g.threshold;
+}
+
+// The hit test of a GOAL instance on ENV's state: (p, v) is MountainCar's, (gx, gy) GridWorld's.
+template <int GOAL, int ENV>
+__device__ __forceinline__ bool goal_test(double p, double v, float gx, float gy,
+                                          const GoalArgs& g) {
+  static_assert(GOAL == kGoalBall || GOAL == kGoalThreshold, "a goal kind");
+  static_assert(GOAL != kGoalBall || ENV == 1, "the ball goal is GridWorld's");
+  if constexpr (GOAL == kGoalBall)
+    return goal_hit(gx, gy, g);
+  else if constexpr (ENV == 0)
+    return goal_hit_threshold(p, v, g);
+  else
+    return goal_hit_threshold((double)gx, (double)gy, g);
 }
 
 // Zeros behind an episode of `len` < T steps of trajectory i: states rows len + 1 .. T, action

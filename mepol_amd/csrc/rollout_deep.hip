@@ -19,12 +19,13 @@
 //                 32, 16, .. 1 (columns past h_L are 0.0), the waves added in order, then + bm[a];
 //   action        mu + noise * exp(log_std), explicit _rn operations.
 //
-// Goal mode (GOAL = true, GridWorld only; mepol_rollout_deep_goal): rollout_mlp_kernel's, with
-// the helpers of goal_mode.hpp.  Thread 0 tests the f32 state after its env step, writes the
-// reward and, on a hit, sets a __shared__ flag before the step's closing barrier; behind that
-// barrier every thread reads the flag and the workgroup leaves the step loop together (no
-// further barrier), then zeroes the rows behind the episode.  Up to each episode's end the
-// records are the bits the GOAL = false instance writes.
+// Goal mode (GOAL = kGoalBall, GridWorld only: mepol_rollout_deep_goal; GOAL = kGoalThreshold,
+// either env: mepol_rollout_deep_goal_threshold): rollout_mlp_kernel's, with the helpers of
+// goal_mode.hpp.  Thread 0 tests the env's state after its step (goal_test), writes the reward
+// and, on a hit, sets a __shared__ flag before the step's closing barrier; behind that barrier
+// every thread reads the flag and the workgroup leaves the step loop together (no further
+// barrier), then zeroes the rows behind the episode.  Up to each episode's end the records are
+// the bits the GOAL = kGoalNone instance writes.
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
@@ -89,7 +90,7 @@ __device__ __forceinline__ double deep_column(const double* __restrict__ sw,
   return acc;
 }
 
-template <int ENV, bool GOAL = false>
+template <int ENV, int GOAL = kGoalNone>
 __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, const double* __restrict__ Wt,
     const double* __restrict__ bt, const double* __restrict__ Wm, const double* __restrict__ bm,
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     float* __restrict__ states_rec, float* __restrict__ actions_rec,
     double* __restrict__ visited, double* __restrict__ final_state, DeepShape sh,
     GoalArgs goal) {
-  static_assert(!GOAL || ENV == 1, "goal mode is GridWorld's");
+  static_assert(GOAL != kGoalBall || ENV == 1, "the ball goal is GridWorld's");
   extern __shared__ double sW[];  // resident rows of W_2^T .. W_L^T, layer after layer
   __shared__ double sx[2];
   __shared__ int sgoal;  // GOAL: the step just taken reached the goal (thread 0 writes it)
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     }
     states_rec[(i * (T + 1)) * 2 + 0] = (float)sx[0];
     states_rec[(i * (T + 1)) * 2 + 1] = (float)sx[1];
-    if constexpr (GOAL) sgoal = 0;
+    if constexpr (GOAL != kGoalNone) sgoal = 0;
   }
   int64_t steps = T;  // GOAL: the episode's length
   // thread 0: exp(log_std) once, and the next step's noise loaded a step ahead (its global
@@ -227,14 +228,14 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
         visited[(i * T + t) * 2 + 0] = sx[0];
         visited[(i * T + t) * 2 + 1] = sx[1];
       }
-      if constexpr (GOAL) {
-        const bool hit = goal_hit(gx, gy, goal);
+      if constexpr (GOAL != kGoalNone) {
+        const bool hit = goal_test<GOAL, ENV>(p, v, gx, gy, goal);
         goal.rewards[i * T + t] = hit ? 1.f : 0.f;
         if (hit) sgoal = 1;
       }
     }
     __syncthreads();
-    if constexpr (GOAL) {
+    if constexpr (GOAL != kGoalNone) {
       if (sgoal) {  // workgroup-uniform: written before the barrier, never cleared
         steps = t + 1;
         break;
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     final_state[2 * i] = sx[0];
     final_state[2 * i + 1] = sx[1];
   }
-  if constexpr (GOAL) {
+  if constexpr (GOAL != kGoalNone) {
     if (j == 0) {
       goal.len[i] = (int)steps;
       goal.done[i] = sgoal;
@@ -307,16 +308,18 @@ static DeepPlan deep_plan(int n_hidden, const int* widths) {
   return p;
 }
 
-// mepol_rollout_deep (goal == nullptr) and mepol_rollout_deep_goal (env 1) behind their argument
-// checks: the same plan, workspace header and launch, the kernel's GOAL instance for the second.
+// mepol_rollout_deep (goal == nullptr), mepol_rollout_deep_goal (kind kGoalBall, env 1) and
+// mepol_rollout_deep_goal_threshold (kind kGoalThreshold) behind their argument checks: the same
+// plan, workspace header and launch, the kernel's GOAL instances for the last two.
 static int deep_run(int env_id, int n_hidden, const int* widths, const double* W1,
                     const double* b1, const double* Wt, const double* bt, const double* Wm,
                     const double* bm, const double* log_std, int a_dim, const double* init64,
                     const float* init32, const double* noise, int64_t n, int64_t T,
                     float* states_rec, float* actions_rec, double* visited, double* final_state,
-                    const GoalArgs* goal, void* workspace, void* stream) {
+                    const GoalArgs* goal, void* workspace, void* stream, int kind = kGoalBall) {
   const DeepPlan p = deep_plan(n_hidden, widths);
   const GoalArgs ga = goal ? *goal : GoalArgs{};
+  if (!goal) kind = kGoalNone;
   hipStream_t st = (hipStream_t)stream;
   if (workspace) MEPOL_HIP(hipMemsetAsync(workspace, 0, kDeepWorkspaceBytes, st));
   const dim3 g((unsigned)n), b(p.threads);
@@ -327,14 +330,33 @@ static int deep_run(int env_id, int n_hidden, const int* widths, const double* W
                        log_std, a_dim, init64, init32, noise, n, T, states_rec, actions_rec,      \
                        visited, final_state, p.sh, ga);                                           \
   } while (0)
-  if (goal)
-    MEPOL_DEEP(1, true);
+  if (kind == kGoalBall)
+    MEPOL_DEEP(1, kGoalBall);
+  else if (kind == kGoalThreshold && env_id == 0)
+    MEPOL_DEEP(0, kGoalThreshold);
+  else if (kind == kGoalThreshold)
+    MEPOL_DEEP(1, kGoalThreshold);
   else if (env_id == 0)
-    MEPOL_DEEP(0, false);
+    MEPOL_DEEP(0, kGoalNone);
   else
-    MEPOL_DEEP(1, false);
+    MEPOL_DEEP(1, kGoalNone);
 #undef MEPOL_DEEP
   MEPOL_CHECK_LAUNCH();
+  return 0;
+}
+
+// Workgroups of the <ENV, GOAL> instance the device holds at once for this shape: the kernel's
+// occupancy at the block size and dynamic LDS the launcher chooses, times the CU count.
+template <int ENV, int GOAL>
+static int deep_resident(int n_hidden, const int* widths, int* resident_workgroups) {
+  const DeepPlan p = deep_plan(n_hidden, widths);
+  int dev = 0, cus = 0, per_cu = 0;
+  MEPOL_HIP(hipGetDevice(&dev));
+  MEPOL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<ENV, GOAL>>(kDeepLdsBytes)));
+  MEPOL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &per_cu, rollout_deep_kernel<ENV, GOAL>, (int)p.threads, p.lds));
+  *resident_workgroups = per_cu * cus;
   return 0;
 }
 
@@ -406,7 +428,7 @@ extern "C" int mepol_rollout_deep_goal(int env_id, int n_hidden, const int* widt
               kDeepWorkspaceBytes);
     return kErrWorkspace;
   }
-  const GoalArgs goal{goal_x, goal_y, radius, rewards_rec, len_out, done_out};
+  const GoalArgs goal{{goal_x}, goal_y, {radius}, rewards_rec, len_out, done_out};
   return deep_run(1, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, nullptr, init32,
                   noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
                   stream);
@@ -423,13 +445,50 @@ extern "C" int mepol_rollout_deep_goal_plan_info(int n_hidden, const int* widths
               kDeepMinL, kDeepMaxL, kDeepMaxH);
     return kErrBadArg;
   }
-  const DeepPlan p = deep_plan(n_hidden, widths);
-  int dev = 0, cus = 0, per_cu = 0;
-  MEPOL_HIP(hipGetDevice(&dev));
-  MEPOL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<1, true>>(kDeepLdsBytes)));
-  MEPOL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, rollout_deep_kernel<1, true>, (int)p.threads, p.lds));
-  *resident_workgroups = per_cu * cus;
-  return 0;
+  return deep_resident<1, kGoalBall>(n_hidden, widths, resident_workgroups);
+}
+
+// mepol_rollout_deep_goal with the threshold test of mepol_rollout_goal_threshold, on either env.
+extern "C" int mepol_rollout_deep_goal_threshold(
+    int env_id, int n_hidden, const int* widths, const double* W1, const double* b1,
+    const double* Wt, const double* bt, const double* Wm, const double* bm, const double* log_std,
+    int a_dim, const double* init64, const float* init32, const double* noise, int64_t n,
+    int64_t T, int coord, double threshold, float* states_rec, float* actions_rec,
+    float* rewards_rec, int32_t* len_out, int32_t* done_out, void* workspace,
+    size_t workspace_bytes, void* stream) {
+  if (n <= 0 || T <= 0) return 0;
+  if (!deep_shape_ok(env_id, n_hidden, widths, a_dim) || a_dim != (env_id == 0 ? 1 : 2) ||
+      T > INT32_MAX || (env_id == 0 && !init64) || (env_id == 1 && !init32) || !W1 || !b1 || !Wt ||
+      !bt || !Wm || !bm || !log_std || !noise || !states_rec || !actions_rec || !rewards_rec ||
+      !len_out || !done_out || (coord != 0 && coord != 1) || threshold != threshold) {
+    set_error("mepol_rollout_deep_goal_threshold: bad arguments (env 0 with a_dim = 1 and init64 "
+              "or env 1 with a_dim = 2 and init32, %d <= n_hidden <= %d, 1 <= width <= %d, coord "
+              "0 or 1, threshold not NaN, no null pointers)",
+              kDeepMinL, kDeepMaxL, kDeepMaxH);
+    return kErrBadArg;
+  }
+  if (workspace && workspace_bytes < kDeepWorkspaceBytes) {
+    set_error("mepol_rollout_deep_goal_threshold: workspace of %zu bytes, %zu needed",
+              workspace_bytes, kDeepWorkspaceBytes);
+    return kErrWorkspace;
+  }
+  const GoalArgs goal = threshold_goal(coord, threshold, rewards_rec, len_out, done_out);
+  return deep_run(env_id, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, init64, init32,
+                  noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace, stream,
+                  kGoalThreshold);
+}
+
+// mepol_rollout_deep_goal_plan_info for the threshold instance of this env.
+extern "C" int mepol_rollout_deep_goal_threshold_plan_info(int env_id, int n_hidden,
+                                                           const int* widths, int a_dim,
+                                                           int* resident_workgroups) {
+  if (!resident_workgroups || !deep_shape_ok(env_id, n_hidden, widths, a_dim) ||
+      a_dim != (env_id == 0 ? 1 : 2)) {
+    set_error("mepol_rollout_deep_goal_threshold_plan_info: bad arguments (env 0 with a_dim = 1 "
+              "or env 1 with a_dim = 2, %d <= n_hidden <= %d, 1 <= width <= %d)",
+              kDeepMinL, kDeepMaxL, kDeepMaxH);
+    return kErrBadArg;
+  }
+  return env_id == 0 ? deep_resident<0, kGoalThreshold>(n_hidden, widths, resident_workgroups)
+                     : deep_resident<1, kGoalThreshold>(n_hidden, widths, resident_workgroups);
 }

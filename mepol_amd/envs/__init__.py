@@ -1,7 +1,7 @@
 from .gridworld import GridWorldContinuous
 from .mountain_car import MountainCarContinuous
 from .spaces import Box
-from .wrappers import CustomRewardEnv, ErgodicEnv, GridGoal, unwrap
+from .wrappers import CustomRewardEnv, ErgodicEnv, GridGoal, ThresholdGoal, unwrap
 
 __all__ = ["GridWorldContinuous", "MountainCarContinuous", "Box", "ErgodicEnv",
-           "CustomRewardEnv", "GridGoal", "unwrap"]
+           "CustomRewardEnv", "GridGoal", "ThresholdGoal", "unwrap"]

@@ -1,6 +1,7 @@
 """ErgodicEnv: ignore the done signal (src/envs/wrappers.py:4-15).  CustomRewardEnv: a reward
-and termination function of the caller's (:40-52), and GridGoal, the GridWorld goals of
-src/experiments/goal_rl.py:61-77 as one such function."""
+and termination function of the caller's (:40-52), and two such functions: GridGoal, the GridWorld
+goals of src/experiments/goal_rl.py:61-77, and ThresholdGoal, the coordinate thresholds of its
+other goals (:91-107)."""
 import numpy as np
 
 
@@ -65,6 +66,25 @@ class GridGoal:
         d = np.asarray(s, dtype=np.float32) - self.goal
         q = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]).astype(np.float32)
         return np.sqrt(q).astype(np.float64) <= self.radius
+
+    def __call__(self, s, r, d, i):
+        return (1, True) if bool(self.hit(s)) else (0, False)
+
+
+class ThresholdGoal:
+    """Sparse goal reward "a state coordinate reaches a threshold", the shape of every
+    non-GridWorld goal of goal_rl.py:91-107 (s[0] >= 7, s[2] >= 3, s[2] >= 1): (1, True) when
+    s[index] >= threshold, else (0, False).  The comparison is in f64 on the env's own state
+    (an f32 state widens exactly), as Python compares an array element with a float, and a NaN
+    state is no hit: the rollout kernels' test (mepol_rollout_goal_threshold)."""
+
+    def __init__(self, index, threshold):
+        self.index = int(index)
+        self.threshold = float(threshold)
+
+    def hit(self, s):
+        """The test for states [..., nf]; a bool array of shape [...]."""
+        return np.asarray(s)[..., self.index].astype(np.float64) >= self.threshold
 
     def __call__(self, s, r, d, i):
         return (1, True) if bool(self.hit(s)) else (0, False)

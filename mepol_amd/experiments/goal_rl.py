@@ -13,6 +13,14 @@ GPU (algorithms/trpo.py):
 widths, so a policy pre-trained with `mepol --hidden_sizes 300 300 300` loads here; policies with
 two to six ReLU layers sample on the one-launch goal rollouts.
 
+--env MountainCarGoal (a build extension: the reference has no MountainCar goal) is the hilltop of
+the MEPOL command line's MountainCar, CustomRewardEnv(MountainCarContinuous(), ThresholdGoal(0,
+0.45)), with that command line's policy ([300, 300], ReLU, log_std_init -0.5), so a policy
+pre-trained with `mepol --env MountainCar` loads with --policy_init.  The goal is gym's own `done`
+for this env: the wall clips the position to exactly 0.45 with velocity 0 when it is crossed, so
+`position >= goal_position and velocity >= 0` is the same condition.  It samples on the one-launch
+threshold-goal rollouts.
+
 MuJoCo goals (AntEscape, AntNavigate, AntJump, HumanoidUp) keep their specs but need mujoco-py,
 which is outside this build's scope.
 """
@@ -71,14 +79,20 @@ def checkpoint_widths(state_dict):
 
 
 def exp_specs():
-    from ..envs import CustomRewardEnv, GridGoal, GridWorldContinuous
+    from ..envs import (CustomRewardEnv, GridGoal, GridWorldContinuous, MountainCarContinuous,
+                        ThresholdGoal)
 
     def grid(goal):
         return dict(env_create=lambda: CustomRewardEnv(GridWorldContinuous(), GridGoal(goal)),
                     hidden_sizes=[300, 300], activation=nn.ReLU, log_std_init=-1.5)
 
+    # the MEPOL command line's MountainCar policy, so that its checkpoints load
+    mountain_car = dict(
+        env_create=lambda: CustomRewardEnv(MountainCarContinuous(), ThresholdGoal(0, 0.45)),
+        hidden_sizes=[300, 300], activation=nn.ReLU, log_std_init=-0.5)
     mujoco = dict(env_create=None, hidden_sizes=[400, 300], activation=nn.ReLU, log_std_init=-0.5)
     return {"GridGoal1": grid((5, 5)), "GridGoal2": grid((2, 5)), "GridGoal3": grid((5, 2)),
+            "MountainCarGoal": mountain_car,
             "AntEscape": dict(mujoco), "AntNavigate": dict(mujoco), "AntJump": dict(mujoco),
             "HumanoidUp": dict(mujoco)}
 

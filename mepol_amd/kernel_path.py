@@ -19,6 +19,9 @@ ROLLOUT_MAX_WIDTH = 512                # one-launch rollouts: csrc/envs.hip, csr
 ROLLOUT_MAX_ACTIONS = 8
 ROLLOUT_FEATURES = 2
 GRIDWORLD_DEFAULTS = (6, 0.2, 2.5)     # (dim, max_delta, wall_width) the kernels' GridWorld has
+# the kernels' MountainCar (csrc/env_step.hpp)
+MOUNTAINCAR_FIELDS = ("min_position", "max_position", "max_speed", "goal_position", "power")
+MOUNTAINCAR_DEFAULTS = (-1.2, 0.6, 0.07, 0.45, 0.0015)
 
 TWO_LAYER, MULTILAYER = "two-layer", "multilayer"
 
@@ -84,33 +87,54 @@ def goal_sampler(env, policy):
     """(goal, layers) when TRPO's sampler (algorithms/trpo.py collect_sample_batch) takes a
     one-launch goal rollout, else None: an f64 policy on the GPU that
     algorithms.mepol._rollout_layers accepts (a 2 -> [h_1 .. h_L] -> a ReLU MLP, widths <= 512),
-    two actions, and a CustomRewardEnv directly over GridWorldContinuous whose reward is a
-    GridGoal.  goal is that GridGoal (its f32 goal and radius are the kernel's arguments).
-    len(layers) names the kernel: the tuple ((W1, b1), (W2, b2)) for ops.rollout_goal, a list
-    [(W1, b1), ..., (W_L, b_L)] of 3 to 6 layers for ops.rollout_deep_goal.  The deep gate has no
+    and a CustomRewardEnv directly over
+      GridWorldContinuous (the default one, two actions) whose reward is a GridGoal (its f32 goal
+                          and radius are the kernel's arguments) or a ThresholdGoal, or
+      MountainCarContinuous (exactly that type with the kernel's constants, one action) whose
+                          reward is a ThresholdGoal (its index, 0 or 1, and threshold are the
+                          kernel's arguments).
+    goal is that reward object; its type and the env's name the kernel's goal kind and env.
+    len(layers) names the kernel: the tuple ((W1, b1), (W2, b2)) for ops.rollout_goal /
+    ops.rollout_goal_threshold, a list [(W1, b1), ..., (W_L, b_L)] of 3 to 6 layers for
+    ops.rollout_deep_goal / ops.rollout_deep_goal_threshold.  The deep gate has no
     ROLLOUT_DEEP_MAX_WORDS cap: that is where the deep kernel stops beating MEPOL's replayed
     per-step graph, and the sampler's only alternative is the host loop.
     MEPOL_TRPO_SAMPLER=host turns the kernel path off."""
     from .algorithms.mepol import _rollout_layers, _rollout_mlp_layers
     from .envs.gridworld import GridWorldContinuous
-    from .envs.wrappers import CustomRewardEnv, GridGoal
+    from .envs.mountain_car import MountainCarContinuous
+    from .envs.wrappers import CustomRewardEnv, GridGoal, ThresholdGoal
 
     if os.environ.get("MEPOL_TRPO_SAMPLER", "kernel") == "host":
         return None
-    if not (type(env) is CustomRewardEnv and type(env.env) is GridWorldContinuous
-            and isinstance(env.get_reward, GridGoal)):
+    if type(env) is not CustomRewardEnv:
         return None
-    # the kernel's GridWorld is the default one: its size, step and walls are constants there
-    if (env.env.dim, env.env.max_delta, env.env.wall_width) != GRIDWORLD_DEFAULTS:
+    goal = env.get_reward
+    if isinstance(goal, ThresholdGoal):
+        if goal.index not in (0, 1) or goal.threshold != goal.threshold:
+            return None
+    elif not isinstance(goal, GridGoal):
+        return None
+    if type(env.env) is GridWorldContinuous:
+        # the kernel's GridWorld is the default one: its size, step and walls are constants there
+        if (env.env.dim, env.env.max_delta, env.env.wall_width) != GRIDWORLD_DEFAULTS:
+            return None
+        a_dim = 2
+    elif type(env.env) is MountainCarContinuous and isinstance(goal, ThresholdGoal):
+        # and so are MountainCar's
+        if tuple(getattr(env.env, k) for k in MOUNTAINCAR_FIELDS) != MOUNTAINCAR_DEFAULTS:
+            return None
+        a_dim = 1
+    else:
         return None
     log_std = getattr(policy, "log_std", None)
     if (log_std is None or not log_std.is_cuda or log_std.dtype != torch.float64
-            or getattr(policy, "action_dim", None) != 2
+            or getattr(policy, "action_dim", None) != a_dim
             or policy.mean.weight.dtype != torch.float64):
         return None
-    layers = (_rollout_mlp_layers(policy, env.num_features, 2)
-              or _rollout_layers(policy, env.num_features, 2, deep=True, word_cap=False))
-    return None if layers is None else (env.get_reward, layers)
+    layers = (_rollout_mlp_layers(policy, env.num_features, a_dim)
+              or _rollout_layers(policy, env.num_features, a_dim, deep=True, word_cap=False))
+    return None if layers is None else (goal, layers)
 
 
 def critic_fit_refusal(vfunc, vfunc_optimizer, states, critic_batch_size):

@@ -1009,6 +1009,129 @@ def rollout_deep_goal(layers, Wm, bm, log_std, init, noise, goal_xy, radius, sta
          ptr(done_out), ptr(ws), ws.numel(), _stream())
 
 
+def _threshold_init(who, env_id, init):
+    """The init tensor's dtype rule of the threshold-goal rollouts: f64 for MountainCar (env_id
+    0), f32 for GridWorld (1); returns (init64, init32) for the C ABI."""
+    if env_id not in (0, 1):
+        raise ValueError(f"{who}: env_id 0 (MountainCar) or 1 (GridWorld)")
+    if init.dtype != (torch.float64 if env_id == 0 else torch.float32):
+        raise ValueError(f"{who}: init is f64 for MountainCar (env_id 0), f32 for GridWorld (1)")
+    return (init, None) if env_id == 0 else (None, init)
+
+
+def rollout_goal_threshold_plan(env_id, n, h0, h1, a_dim=None):
+    """rollout_goal_plan for rollout_goal_threshold on this env: the form the occupancy of the
+    instance that runs (env x threshold goal) gives.  a_dim defaults to the env's."""
+    a_dim = (1 if env_id == 0 else 2) if a_dim is None else a_dim
+    wg, kc = ctypes.c_int(), ctypes.c_int()
+    call("mepol_rollout_goal_threshold_plan_info", env_id, n, h0, h1, a_dim, ctypes.byref(wg),
+         ctypes.byref(kc))
+    return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
+
+
+def rollout_goal_threshold(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, coord, threshold,
+                           states_rec, actions_rec, rewards_rec, len_out, done_out,
+                           defer_check=False):
+    """rollout_goal with a threshold goal, on MountainCar (env_id 0, init f64 [n,2], one action)
+    or GridWorld (1, init f32, two actions): a trajectory ends at the first step whose state has
+    state[coord] >= threshold, compared in f64 on the env's own state (reward 1, done), or after T
+    steps.  coord is 0 or 1; the threshold may be +-inf, not NaN.  Outputs, the error word,
+    defer_check and the re-run of the one-workgroup form as rollout_goal."""
+    _require_device(init, noise, states_rec, actions_rec, rewards_rec, len_out, done_out, W1, b1,
+                    W2, b2, Wm, bm, log_std)
+    T, n, a_dim = noise.shape
+    h0, h1 = W1.shape[0], W2.shape[0]
+    if (tuple(W1.shape) != (h0, 2) or tuple(W2.shape) != (h1, h0) or tuple(Wm.shape) != (a_dim, h1)
+            or tuple(init.shape) != (n, 2) or tuple(states_rec.shape) != (n, T + 1, 2)
+            or tuple(actions_rec.shape) != (n, T, a_dim) or tuple(rewards_rec.shape) != (n, T)
+            or len_out.numel() != n or done_out.numel() != n):
+        raise ValueError("rollout_goal_threshold: tensor shapes do not fit the policy / batch")
+    if (any(t.dtype != torch.float64 for t in (W1, b1, W2, b2, Wm, bm, log_std, noise))
+            or any(t.dtype != torch.float32 for t in (states_rec, actions_rec, rewards_rec))
+            or len_out.dtype != torch.int32 or done_out.dtype != torch.int32
+            or not all(t.is_contiguous() for t in (states_rec, actions_rec, rewards_rec, len_out,
+                                                   done_out))):
+        raise ValueError("rollout_goal_threshold: f64 policy / noise, f32 contiguous records, "
+                         "int32 len / done")
+    W2t = W2.t().contiguous()
+    # (contiguous copies stay referenced until the launch is queued)
+    W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
+                                                                          log_std, init, noise))
+    init64, init32 = _threshold_init("rollout_goal_threshold", env_id, init)
+    ws = _ws_or_cached(None, init.device, "rollout", "rollout_goal_threshold", env_id, n, T, h0,
+                       h1, a_dim)
+    args = (env_id, ptr(W1), ptr(b1), h0, ptr(W2t), ptr(b2), h1, ptr(Wm), ptr(bm), ptr(log_std),
+            a_dim, ptr(init64), ptr(init32), ptr(noise), n, T, int(coord), float(threshold),
+            ptr(states_rec), ptr(actions_rec), ptr(rewards_rec), ptr(len_out), ptr(done_out))
+    keep = (W1, b1, W2t, b2, Wm, bm, log_std, init, noise)
+    call("mepol_rollout_goal_threshold", *args, ptr(ws), ws.numel(), _stream())
+
+    def rerun(_keep=keep):
+        import warnings
+
+        warnings.warn("mepol_rollout_goal_threshold: workgroups of a trajectory were not "
+                      "co-resident; re-ran the one-workgroup form")
+        call("mepol_rollout_goal_threshold", *args, None, 0, _stream())
+
+    err = ws[:4].view(torch.int32)
+    if defer_check:
+        return err, rerun
+    if n > 0 and T > 0 and int(err[0].item()) != 0:
+        rerun()
+    return None
+
+
+def rollout_deep_goal_threshold_plan(env_id, widths, a_dim=None):
+    """rollout_deep_goal_plan for rollout_deep_goal_threshold on this env (the occupancy of the
+    instance that runs times the CU count).  a_dim defaults to the env's."""
+    a_dim = (1 if env_id == 0 else 2) if a_dim is None else a_dim
+    wg = ctypes.c_int()
+    arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
+    call("mepol_rollout_deep_goal_threshold_plan_info", env_id, len(widths), arr, a_dim,
+         ctypes.byref(wg))
+    return {"resident_workgroups": wg.value}
+
+
+def rollout_deep_goal_threshold(env_id, layers, Wm, bm, log_std, init, noise, coord, threshold,
+                                states_rec, actions_rec, rewards_rec, len_out, done_out):
+    """rollout_goal_threshold for a ReLU policy with 3 to 6 hidden layers, layers = [(W1, b1), ...,
+    (W_L, b_L)] as rollout_deep takes them: one launch with one workgroup per trajectory
+    (csrc/rollout_deep.hip, threshold instance), no error word to check."""
+    _require_device(init, noise, states_rec, actions_rec, rewards_rec, len_out, done_out, Wm, bm,
+                    log_std, *[t for p in layers for t in p])
+    T, n, a_dim = noise.shape
+    (W1, b1), rest = layers[0], layers[1:]
+    fan_in = [2] + [W.shape[0] for W, _ in layers]
+    if (any(tuple(W.shape) != (b.numel(), f) for (W, b), f in zip(layers, fan_in))
+            or tuple(Wm.shape) != (a_dim, fan_in[-1]) or bm.numel() != a_dim
+            or log_std.numel() != a_dim or tuple(init.shape) != (n, 2)
+            or tuple(states_rec.shape) != (n, T + 1, 2) or tuple(actions_rec.shape) != (n, T, a_dim)
+            or tuple(rewards_rec.shape) != (n, T) or len_out.numel() != n
+            or done_out.numel() != n):
+        raise ValueError("rollout_deep_goal_threshold: tensor shapes do not fit the policy / batch")
+    f64 = [t for p in layers for t in p] + [Wm, bm, log_std, noise]
+    if (any(t.dtype != torch.float64 for t in f64)
+            or any(t.dtype != torch.float32 for t in (states_rec, actions_rec, rewards_rec))
+            or len_out.dtype != torch.int32 or done_out.dtype != torch.int32
+            or not all(t.is_contiguous() for t in (states_rec, actions_rec, rewards_rec, len_out,
+                                                   done_out))):
+        raise ValueError("rollout_deep_goal_threshold: f64 policy / noise, f32 contiguous records, "
+                         "int32 len / done")
+    widths = (ctypes.c_int * len(layers))(*[W.shape[0] for W, _ in layers])
+    Wt = torch.cat([W.t().reshape(-1) for W, _ in rest])
+    bt = torch.cat([b.reshape(-1) for _, b in rest])
+    # (contiguous copies stay referenced until the launch is queued)
+    W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
+                                                                     noise))
+    init64, init32 = _threshold_init("rollout_deep_goal_threshold", env_id, init)
+    ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
+                       a_dim)
+    call("mepol_rollout_deep_goal_threshold", env_id, len(layers), widths, ptr(W1), ptr(b1),
+         ptr(Wt), ptr(bt), ptr(Wm), ptr(bm), ptr(log_std), a_dim, ptr(init64), ptr(init32),
+         ptr(noise), n, T, int(coord), float(threshold), ptr(states_rec), ptr(actions_rec),
+         ptr(rewards_rec), ptr(len_out), ptr(done_out), ptr(ws), ws.numel(), _stream())
+
+
 def traj_budget(lens, dones, budget):
     """The step budget over a parallel batch (mepol_traj_budget): trajectories in index order until
     `budget` steps are kept, the last one cut.  lens, dones: int32 [n] on the device.  Returns

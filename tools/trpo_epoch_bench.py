@@ -5,10 +5,14 @@ batch 24,000, traj_len 1200, policy 2 -> [300, 300] -> 2, cg_iters 20, kl_thresh
     python tools/trpo_epoch_bench.py --batch_size 2400 --traj_len 120 --reps 3
     python tools/trpo_epoch_bench.py --hidden_sizes 300 300 300 \
         --out profiles/trpo_epoch_bench_deep.json
+    python tools/trpo_epoch_bench.py --env MountainCarGoal    the goal_rl spec of that name (policy
+                                          2 -> [300, 300] -> 1, log_std -0.5; random weights only),
+                                          JSON to profiles/trpo_epoch_bench_mc.json
 
 Per epoch, the median [min, max] over --reps epochs after --warmup:
   sample_kernel   collect_sample_batch on the kernel path (rounds of ops.rollout_goal, or of
-                  ops.rollout_deep_goal for 3 to 6 hidden layers, + ops.traj_budget);
+                  ops.rollout_deep_goal for 3 to 6 hidden layers, + ops.traj_budget; for
+                  MountainCarGoal their threshold-goal forms);
   sample_host     collect_sample_batch on the reference-shaped host loop in the same process
                   (MEPOL_TRPO_SAMPLER=host): one policy.predict and one env.step per step.  It
                   is the comparison point of the sampler and takes seconds, so it has its own
@@ -37,13 +41,18 @@ GOAL = (5, 5)  # GridGoal1
 GAMMA, LAMBD, KL_THRESH, CG_DAMPING = 0.995, 0.98, 0.001, 0.1
 
 
-def _policies(dev, hidden=None):
+ENVS = ("GridGoal1", "MountainCarGoal")
+
+
+def _policies(dev, hidden=None, env_name="GridGoal1"):
     import numpy as np
     import torch
 
     from mepol_amd.policy import GaussianPolicy
 
     torch.manual_seed(7)
+    if env_name == "MountainCarGoal":
+        return {"random": GaussianPolicy(hidden or [300, 300], 2, 1, -0.5).to(dev)}
     random = GaussianPolicy(hidden or [300, 300], 2, 2, -1.5).to(dev)
     if hidden:
         return {"random": random}
@@ -78,22 +87,32 @@ def main(argv=None):
     p.add_argument("--host_reps", type=int, default=1)
     p.add_argument("--hidden_sizes", type=int, nargs="+", default=None, metavar="N",
                    help="hidden widths of the policy; default [300, 300]")
-    p.add_argument("--out", default=os.path.join(HERE, "profiles", "trpo_epoch_bench.json"))
+    p.add_argument("--env", choices=ENVS, default="GridGoal1",
+                   help="the goal_rl experiment whose env and policy shape are timed")
+    p.add_argument("--out", default=None,
+                   help="default profiles/trpo_epoch_bench.json (MountainCarGoal: "
+                        "profiles/trpo_epoch_bench_mc.json)")
     args = p.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join(HERE, "profiles", "trpo_epoch_bench_mc.json"
+                                if args.env == "MountainCarGoal" else "trpo_epoch_bench.json")
     sys.path.insert(0, HERE)
     import torch
 
     from mepol_amd.algorithms import trpo as T
     from mepol_amd.envs import CustomRewardEnv, GridGoal, GridWorldContinuous
-    from mepol_amd.experiments.goal_rl import create_critic
+    from mepol_amd.experiments.goal_rl import create_critic, exp_specs
 
     dev = torch.device("cuda")
-    env = CustomRewardEnv(GridWorldContinuous(), GridGoal(GOAL))
+    if args.env == "GridGoal1":
+        env = CustomRewardEnv(GridWorldContinuous(), GridGoal(GOAL))
+    else:
+        env = exp_specs()[args.env]["env_create"]()
     env.seed(0)
     B, L = args.batch_size, args.traj_len
     rows = {}
     batch = None
-    for name, policy in _policies(dev, args.hidden_sizes).items():
+    for name, policy in _policies(dev, args.hidden_sizes, args.env).items():
         os.environ["MEPOL_TRPO_SAMPLER"] = "kernel"
         ms, rounds, trajs, dones = [], [], [], []
         for i in range(args.warmup + args.reps):
@@ -120,7 +139,7 @@ def main(argv=None):
         print(json.dumps({k: v for k, v in rows.items() if k.endswith(name)}), flush=True)
 
     # the rest of the epoch on the random policy's last batch
-    policy = _policies(dev, args.hidden_sizes)["random"]
+    policy = _policies(dev, args.hidden_sizes, args.env)["random"]
     vfunc = create_critic(2).to(device=dev, dtype=torch.float64)
     states, actions, rewards, lens, done = batch
     m, _, nf = states.shape
@@ -159,6 +178,8 @@ def main(argv=None):
                         "cg_iters": args.cg_iters, "kl_thresh": KL_THRESH},
               "run": {"reps": args.reps, "warmup": args.warmup, "host_reps": args.host_reps},
               "device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.env != "GridGoal1":
+        result["shape"]["env"] = args.env
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)

@@ -36,8 +36,8 @@ extern "C" {
  * workspace; mepol_gemm_dpp removed; 3: mepol_iw_normalize_gathered takes the per-rank
  * trajectory sums).  Additions keep the number: the *_plan_info queries, mepol_critic_fit with
  * mepol_critic_fit_plan_info, mepol_rollout_deep_goal with
- * mepol_rollout_deep_goal_plan_info, and the five mepol_rollout_*goal_threshold* entry points
- * came in at 4.  mepol_abi_version() returns the library's value. */
+ * mepol_rollout_deep_goal_plan_info, the five mepol_rollout_*goal_threshold* entry points,
+ * mepol_traj_cut and mepol_rollout_deep_plan_info came in at 4.  mepol_abi_version() returns the library's value. */
 #define MEPOL_ABI_VERSION 4
 
 #define MEPOL_ERR_BAD_ARG 1001
@@ -217,6 +217,13 @@ int mepol_rollout_deep(int env_id, int n_hidden, const int* widths, const double
 /* Workspace of mepol_rollout_deep at these sizes: 256 bytes (the error-word header). */
 int mepol_rollout_deep_workspace_size(int64_t n, int64_t T, int n_hidden, const int* widths,
                                       int a_dim, size_t* bytes);
+/* Workgroups (= trajectories) of mepol_rollout_deep itself the device holds at once at this
+ * shape: the occupancy of the instance without a goal on this env at the launcher's block size
+ * and dynamic LDS, times the number of compute units (mepol_rollout_deep_goal_plan_info reports
+ * the goal instance's).  Shapes outside mepol_rollout_deep's and a null pointer are
+ * MEPOL_ERR_BAD_ARG, checked before the device is asked. */
+int mepol_rollout_deep_plan_info(int env_id, int n_hidden, const int* widths, int a_dim,
+                                 int* resident_workgroups);
 
 /* ---- TRPO sampling and batch processing (src/algorithms/trpo.py:86-201, 308-331) -------------
  * Every entry point below takes device pointers, only enqueues, returns 0 without a launch for
@@ -326,6 +333,20 @@ int mepol_rollout_deep_goal_threshold_plan_info(int env_id, int n_hidden, const 
 int mepol_traj_budget(const int32_t* len, const int32_t* done, int64_t n, int64_t budget,
                       int32_t* len_out, int32_t* done_out, int64_t* offsets, int64_t* meta,
                       void* stream);
+/* The episodes inside n un-terminated rollouts of T steps: trajectory i is cut at the first step
+ * whose reached state ends the episode, with the outputs of the goal-mode rollouts
+ * (mepol_rollout_goal), so that later stages cannot tell the routes apart.  done_step [n,T]
+ * bytes: non-zero (any value) = the state reached by step t ends the episode.  With f the
+ * smallest such t, len[i] = f + 1 and done[i] = 1; without one, len[i] = T and done[i] = 0.
+ * rewards [n,T] f32 (in/out) holds the per-step rewards: rewards[i, t] for t < len[i] is not
+ * touched (NaN payloads and -0.0 keep their bits); rewards[i, len ..], actions_rec[i, len ..]
+ * ([n,T,a_dim] f32) and states_rec[i, len + 1 ..] ([n,T+1,num_features] f32) become +0.0f.  One
+ * workgroup of 256 threads per trajectory, no communication between workgroups.  n = 0 returns 0
+ * without a launch; a null pointer, n < 0, T <= 0, T > INT32_MAX - 1, num_features <= 0 or
+ * a_dim <= 0 is MEPOL_ERR_BAD_ARG, checked on the host before any launch. */
+int mepol_traj_cut(const uint8_t* done_step, int64_t n, int64_t T, float* rewards,
+                   float* states_rec, int num_features, float* actions_rec, int a_dim,
+                   int32_t* len, int32_t* done, void* stream);
 /* process_traj (trpo.py:175-201) over n ragged trajectories and the concatenation of :308-326.
  * rewards [n,T] f32, values [n,T+1] f64 (the critic at every recorded state), len / done / offsets
  * as mepol_traj_budget writes them, states_rec [n,T+1,num_features] f32, actions_rec [n,T,a_dim]

@@ -114,6 +114,8 @@ SIGNATURES = {
                            _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp],
     "mepol_rollout_deep_workspace_size": [_c_i64, _c_i64, _c_int, ctypes.POINTER(_c_int), _c_int,
                                           ctypes.POINTER(_c_sz)],
+    "mepol_rollout_deep_plan_info": [_c_int, _c_int, ctypes.POINTER(_c_int), _c_int,
+                                     ctypes.POINTER(_c_int)],
     "mepol_rollout_goal": [_c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
                            _c_int, _c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_float, ctypes.c_float,
                            _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp],
@@ -142,6 +144,8 @@ SIGNATURES = {
     "mepol_rollout_deep_goal_threshold_plan_info": [_c_int, _c_int, ctypes.POINTER(_c_int), _c_int,
                                                     ctypes.POINTER(_c_int)],
     "mepol_traj_budget": [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],
+    "mepol_traj_cut": [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_vp,
+                       _c_vp],
     "mepol_gae": [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_dbl, _c_dbl, _c_vp,
                   _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],
     "mepol_standardize_workspace_size": [_c_i64, ctypes.POINTER(_c_sz)],

@@ -40,10 +40,6 @@ int_type = torch.int64
 # ---------------------------------------------------------------------------------------------
 # Rollout
 # ---------------------------------------------------------------------------------------------
-def _batched_kind(env):
-    return getattr(type(unwrap(env)), "batched_kind", None)
-
-
 class _RolloutGraph:
     """The T-step rollout of a HIP-stepped env as one replayed HIP graph.
 
@@ -188,7 +184,8 @@ def collect_particles_device(env, policy, num_traj, traj_len, state_filter, gene
 
     Returns device tensors: states f32 [nt, T+1, nf], actions f32 [nt, T, a], real lengths
     int32 [nt, 1], next_states f32 [N, ns] (particle p = n*T + t <-> s_{n, t+1}, mepol.py:98-109).
-    MountainCar / GridWorld step in a HIP kernel (one fused launch per step after the MLP);
+    MountainCar / GridWorld with the kernels' constants (kernel_path.kernel_env) step in a HIP
+    kernel (one fused launch per step after the MLP, or all steps in one launch);
     any other env is stepped on the host in lockstep with one batched policy call per step.
     `visited` (optional, f64 [nt, T, nf]) receives the env's own state after every step (f64
     MountainCar state / GridWorld f32 state, not the f32 particle copy), for the heatmap.
@@ -203,7 +200,9 @@ def collect_particles_device(env, policy, num_traj, traj_len, state_filter, gene
     if dev.type != "cuda":
         raise RuntimeError("collect_particles_device needs the policy on a ROCm device")
     base = unwrap(env)
-    kind = _batched_kind(env)
+    # the HIP env steps hold the default envs' constants: any other MountainCar / GridWorld (a
+    # subclass, another dim or power) is stepped on the host like an env without a kernel
+    env_id = kernel_path.kernel_env(base)
     nf = env.num_features
     a_dim = env.action_space.shape[0]
     T = int(traj_len)
@@ -216,10 +215,9 @@ def collect_particles_device(env, policy, num_traj, traj_len, state_filter, gene
     states = torch.zeros((num_traj, T + 1, nf), dtype=torch.float32, device=dev)
     actions = torch.zeros((num_traj, T, a_dim), dtype=torch.float32, device=dev)
     with torch.no_grad():
-        if kind in ("mountaincar", "gridworld"):
-            states, actions = _rollout_hip_stepped(0 if kind == "mountaincar" else 1, base, policy,
-                                                   total, lo, hi, generator, visited, states,
-                                                   actions)
+        if env_id is not None:
+            states, actions = _rollout_hip_stepped(env_id, base, policy, total, lo, hi, generator,
+                                                   visited, states, actions)
         elif world > 1:
             raise NotImplementedError("sharded rollouts need a batched (HIP-stepped) env")
         else:

@@ -31,7 +31,10 @@ whole rounds of trajectories out in one launch each (ops.rollout_goal for two la
 ops.rollout_deep_goal for three to six: termination and the sparse reward inside the kernel; for
 a threshold goal, on GridWorld or MountainCar, ops.rollout_goal_threshold and
 ops.rollout_deep_goal_threshold), applies the reference's step budget on the device
-(ops.traj_budget) and reads two or three words per round;
+(ops.traj_budget) and reads two or three words per round.  Any other reward of the reached state
+alone (envs.BatchReward: BoxGoal, AnyGoal, a user's own; kernel_path.cut_sampler) takes the same
+rounds on the un-terminated one-launch rollouts (ops.rollout_mlp, ops.rollout_deep), one batched
+reward call per round and ops.traj_cut, which cuts every trajectory at its first done;
 process_batch computes targets, GAE advantages and the packed batch with ops.gae and
 ops.standardize.  Every other env, policy or device takes the reference's sequential loop, and
 CPU tensors a numpy restatement of the same arithmetic.
@@ -365,29 +368,33 @@ def trpo_step(policy, states, actions, advantages, kl_thresh, cg_iters=10, cg_da
 # ---------------------------------------------------------------------------------------------
 # Sampling (trpo.py:86-172)
 # ---------------------------------------------------------------------------------------------
-# What the last collect_sample_batch call did: "path" is "kernel" or "host", "rounds" the kernel
-# path's rollout launches; "kernel_batches" / "host_batches" count calls since import.
-SAMPLER_STATS = {"path": None, "rounds": 0, "kernel_batches": 0, "host_batches": 0}
+# What the last collect_sample_batch call did: "path" is "kernel" (a goal-mode rollout), "cut" (an
+# un-terminated rollout cut by a BatchReward) or "host", "rounds" the rollout launches of the two
+# kernel routes; "kernel_batches" / "cut_batches" / "host_batches" count calls since import.
+SAMPLER_STATS = {"path": None, "rounds": 0, "kernel_batches": 0, "host_batches": 0,
+                 "cut_batches": 0}
 
 ROUND_MAX_TRAJ = 65536  # mepol_traj_budget's limit
 _ROUND_CAPACITY = {}
 
 
 BALL, THRESHOLD = "ball", "threshold"  # the goal kinds of the rollout kernels
-MOUNTAINCAR, GRIDWORLD = 0, 1          # their env_id
+CUT = "cut"                            # no goal in the kernel: the un-terminated rollouts
+MOUNTAINCAR, GRIDWORLD = kernel_path.MOUNTAINCAR, kernel_path.GRIDWORLD  # their env_id
 
 
 def _round_capacity(h0, h1, a_dim, device, env_id=GRIDWORLD, kind=BALL):
     """Trajectories per round that cost no more time than one: the most for which the plan of
     the instance that runs (ops.rollout_goal_plan for GridWorld's ball goal,
-    ops.rollout_goal_threshold_plan for a threshold goal on env_id: each kernel's own occupancy)
-    still reports the multi-workgroup form, found once per shape, env, goal kind and
-    MEPOL_ROLLOUT_MW setting by bisection, or, where there is no such form, one workgroup per
-    CU."""
+    ops.rollout_goal_threshold_plan for a threshold goal on env_id, ops.rollout_mlp_plan for the
+    cut route's un-terminated rollout: each kernel's own occupancy) still reports the
+    multi-workgroup form, found once per shape, env, kind (so route) and MEPOL_ROLLOUT_MW setting
+    by bisection, or, where there is no such form, one workgroup per CU."""
     key = (h0, h1, a_dim, device, os.environ.get("MEPOL_ROLLOUT_MW"), env_id, kind)
     if key not in _ROUND_CAPACITY:
         def multi(n):
             plan = (ops.rollout_goal_plan(n, h0, h1, a_dim) if kind == BALL
+                    else ops.rollout_mlp_plan(n, h0, h1, a_dim) if kind == CUT
                     else ops.rollout_goal_threshold_plan(env_id, n, h0, h1, a_dim))
             return plan["workgroups_per_traj"] > 1
 
@@ -401,13 +408,14 @@ def _round_capacity(h0, h1, a_dim, device, env_id=GRIDWORLD, kind=BALL):
 
 def _round_capacity_deep(widths, a_dim, device, env_id=GRIDWORLD, kind=BALL):
     """_round_capacity for a policy with 3 to 6 hidden layers: the trajectories (one workgroup
-    each) the device holds at once (ops.rollout_deep_goal_plan, or
-    ops.rollout_deep_goal_threshold_plan for a threshold goal on env_id), found once per shape,
-    env, goal kind and MEPOL_ROLLOUT_KL setting (the resident rows set the kernel's LDS, so its
-    occupancy)."""
+    each) the device holds at once (ops.rollout_deep_goal_plan, ops.rollout_deep_goal_threshold_plan
+    for a threshold goal on env_id, or ops.rollout_deep_plan for the cut route's un-terminated
+    rollout), found once per shape, env, kind (so route) and MEPOL_ROLLOUT_KL setting (the
+    resident rows set the kernel's LDS, so its occupancy)."""
     key = (tuple(widths), a_dim, device, os.environ.get("MEPOL_ROLLOUT_KL"), env_id, kind)
     if key not in _ROUND_CAPACITY:
         plan = (ops.rollout_deep_goal_plan(widths, a_dim) if kind == BALL
+                else ops.rollout_deep_plan(env_id, widths, a_dim) if kind == CUT
                 else ops.rollout_deep_goal_threshold_plan(env_id, widths, a_dim))
         _ROUND_CAPACITY[key] = max(plan["resident_workgroups"], 1)
     return _ROUND_CAPACITY[key]
@@ -421,17 +429,89 @@ def _draw_round(base, R, T, a_dim, device, generator):
     return init, noise
 
 
-def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, round_traj):
+def _goal_round(goal, layers, head, env_id):
+    """(fill, cap kind) of the in-kernel goal route: fill(init, noise, states, actions, rewards)
+    runs one round on the GOAL instance of env x goal kind (kernel_path.goal_sampler admits no
+    other pair) and returns (lens, dones, err, rerun), the last two None for the deep rollouts,
+    which have no error word and so no re-run."""
+    deep = len(layers) > 2
+    kind = THRESHOLD if isinstance(goal, ThresholdGoal) else BALL
+    test = (goal.goal, goal.radius) if kind == BALL else (goal.index, goal.threshold)
+
+    def fill(init, noise, states, actions, rewards):
+        R = init.shape[0]
+        lens = torch.empty(R, dtype=torch.int32, device=init.device)
+        dones = torch.empty(R, dtype=torch.int32, device=init.device)
+        roll = (*head, init, noise, *test, states, actions, rewards, lens, dones)
+        if deep:
+            if kind == BALL:
+                ops.rollout_deep_goal(layers, *roll)
+            else:
+                ops.rollout_deep_goal_threshold(env_id, layers, *roll)
+            return lens, dones, None, None
+        (W1, b1), (W2, b2) = layers
+        if kind == BALL:
+            err, rerun = ops.rollout_goal(W1, b1, W2, b2, *roll, defer_check=True)
+        else:
+            err, rerun = ops.rollout_goal_threshold(env_id, W1, b1, W2, b2, *roll,
+                                                    defer_check=True)
+        return lens, dones, err, rerun
+
+    return fill, kind
+
+
+def _cut_round(goal, layers, head, env_id):
+    """(fill, cap kind) of the "roll out, then cut" route (kernel_path.cut_sampler): fill rolls
+    the round out UN-terminated in one launch (ops.rollout_mlp, which handles its own error word,
+    or ops.rollout_deep), evaluates the BatchReward once over the env's own state after every
+    step (MountainCar's f64 `visited`; GridWorld's f32 records widened, which is exact) and cuts
+    every trajectory at its first done (ops.traj_cut): the outputs of a goal-mode rollout."""
+    deep = len(layers) > 2
+    who = type(goal).__name__
+
+    def fill(init, noise, states, actions, rewards):
+        R, T = init.shape[0], noise.shape[0]
+        visited = (torch.empty((R, T, 2), dtype=torch.float64, device=init.device)
+                   if env_id == MOUNTAINCAR else None)
+        if deep:
+            ops.rollout_deep(env_id, layers, *head, init, noise, states, actions, visited=visited)
+        else:
+            ops.rollout_mlp(env_id, *layers[0], *layers[1], *head, init, noise, states, actions,
+                            visited=visited)
+        env_states = visited if visited is not None else states[:, 1:].to(torch.float64)
+        out = goal.batch(env_states)
+        if not (isinstance(out, tuple) and len(out) == 2 and all(torch.is_tensor(x) for x in out)):
+            raise ValueError(f"{who}.batch must return (reward, done), two tensors")
+        reward, done = out
+        if tuple(reward.shape) != (R, T) or tuple(done.shape) != (R, T):
+            raise ValueError(f"{who}.batch must return reward and done of shape [n, T] = "
+                             f"{(R, T)}; got {tuple(reward.shape)} and {tuple(done.shape)}")
+        if done.dtype != torch.bool or not reward.is_floating_point():
+            raise ValueError(f"{who}.batch must return a float reward and a bool done; got "
+                             f"{reward.dtype} and {done.dtype}")
+        if reward.device != init.device or done.device != init.device:
+            raise ValueError(f"{who}.batch must keep its results on the states' device")
+        rewards.copy_(reward)  # rounds to f32
+        lens, dones = ops.traj_cut(done.contiguous(), rewards, states, actions)
+        return lens, dones, None, None
+
+    return fill, CUT
+
+
+def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, round_traj,
+                    cut_env=None):
+    """The round loop of both kernel routes: goal_sampler's (cut_env None; termination inside the
+    rollout kernel) and cut_sampler's (cut_env = its env_id).  Only `fill`, the part that leaves
+    (states, actions, rewards, lens, dones) of a round, differs."""
     dev = policy.device
     base = unwrap(env)
     a_dim = policy.action_dim
-    deep = len(layers) > 2  # the deep rollouts have no error word, so no re-run
-    # the kernel instance: env x goal kind (kernel_path.goal_sampler admits no other pair)
-    env_id = MOUNTAINCAR if type(base).batched_kind == "mountaincar" else GRIDWORLD
-    kind = THRESHOLD if isinstance(goal, ThresholdGoal) else BALL
+    env_id = kernel_path.kernel_env(base) if cut_env is None else cut_env
     widths = [W.shape[0] for W, _ in layers]
     head = (policy.mean.weight.detach(), policy.mean.bias.detach(), policy.log_std.detach())
-    cap = (_round_capacity_deep(widths, a_dim, dev, env_id, kind) if deep
+    fill, kind = (_goal_round if cut_env is None else _cut_round)(goal, layers, head, env_id)
+    # the occupancy of the instance that runs
+    cap = (_round_capacity_deep(widths, a_dim, dev, env_id, kind) if len(layers) > 2
            else _round_capacity(*widths, a_dim, dev, env_id, kind))
     steps_idx = torch.arange(T + 1, device=dev)
     remaining, rounds, parts = int(batch_size), 0, []
@@ -443,28 +523,14 @@ def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, r
         states = torch.empty((R, T + 1, 2), dtype=torch.float32, device=dev)
         actions = torch.empty((R, T, a_dim), dtype=torch.float32, device=dev)
         rewards = torch.empty((R, T), dtype=torch.float32, device=dev)
-        lens = torch.empty(R, dtype=torch.int32, device=dev)
-        dones = torch.empty(R, dtype=torch.int32, device=dev)
         if env_id == GRIDWORLD:
             init = init.to(torch.float32)
-        test = (goal.goal, goal.radius) if kind == BALL else (goal.index, goal.threshold)
-        roll = (*head, init, noise, *test, states, actions, rewards, lens, dones)
-        if deep:
-            if kind == BALL:
-                ops.rollout_deep_goal(layers, *roll)
-            else:
-                ops.rollout_deep_goal_threshold(env_id, layers, *roll)
-            kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
+        lens, dones, err, rerun = fill(init, noise, states, actions, rewards)
+        kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
+        if err is None:
             # the round's one host synchronisation: {trajectories used, steps kept}
             m, kept = meta.tolist()
         else:
-            (W1, b1), (W2, b2) = layers
-            if kind == BALL:
-                err, rerun = ops.rollout_goal(W1, b1, W2, b2, *roll, defer_check=True)
-            else:
-                err, rerun = ops.rollout_goal_threshold(env_id, W1, b1, W2, b2, *roll,
-                                                        defer_check=True)
-            kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)
             # the round's one host synchronisation: {trajectories used, steps kept, error word}
             m, kept, bad = torch.cat([meta, err.to(torch.int64)]).tolist()
             if bad:
@@ -480,8 +546,9 @@ def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, r
         rewards[m - 1].masked_fill_(steps_idx[:T] >= last, 0)
         parts.append((states[:m], actions[:m], rewards[:m], kept_len[:m], kept_done[:m]))
         remaining -= kept
-    SAMPLER_STATS.update(path="kernel", rounds=rounds)
-    SAMPLER_STATS["kernel_batches"] += 1
+    path = "kernel" if cut_env is None else "cut"
+    SAMPLER_STATS.update(path=path, rounds=rounds)
+    SAMPLER_STATS[path + "_batches"] += 1
     st, ac, rw, ln, dn = (torch.cat(x) if len(parts) > 1 else x[0] for x in zip(*parts))
     return st, ac, rw, ln.reshape(-1, 1), dn.reshape(-1, 1).bool()
 
@@ -531,15 +598,23 @@ def collect_sample_batch(env, policy, batch_size, traj_len, num_workers=1, gener
     trajectories the multi-workgroup rollout holds (_round_capacity; for 3 to 6 hidden layers
     the workgroups the device holds at once, _round_capacity_deep).  `generator` seeds the
     draws; `draw(R, T, a, device) -> (init [R, 2] in the env's dtype, GridWorld f32 / MountainCar
-    f64, noise f64 [T, R, a])` replaces them (tests).  num_workers is ignored there.  Everything
-    else runs the reference's sequential loop with one worker."""
+    f64, noise f64 [T, R, a])` replaces them (tests).  num_workers is ignored there.
+
+    Where kernel_path.cut_sampler takes them instead (any BatchReward: a reward of the reached
+    state alone), the same rounds run un-terminated and are cut at each trajectory's first done
+    (_cut_round); the draws, the budget and the results' layout are the goal route's, and a round
+    always costs traj_len steps.  Everything else runs the reference's sequential loop with one
+    worker."""
     if not hasattr(env.action_space, "shape") or hasattr(env.action_space, "n"):
         raise NotImplementedError("collect_sample_batch: continuous action spaces only")
-    spec = kernel_path.goal_sampler(env, policy)
-    if spec is not None and batch_size > 0:
-        with torch.no_grad():
-            return _collect_kernel(env, policy, *spec, batch_size, int(traj_len), generator, draw,
-                                   round_traj)
+    if batch_size > 0:
+        spec = kernel_path.goal_sampler(env, policy)
+        cut = kernel_path.cut_sampler(env, policy) if spec is None else None
+        if spec is not None or cut is not None:
+            goal, layers, cut_env = (*spec, None) if spec is not None else cut
+            with torch.no_grad():
+                return _collect_kernel(env, policy, goal, layers, batch_size, int(traj_len),
+                                       generator, draw, round_traj, cut_env=cut_env)
     return _collect_host(env, policy, int(batch_size), int(traj_len))
 
 

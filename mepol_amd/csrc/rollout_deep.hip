@@ -397,6 +397,17 @@ extern "C" int mepol_rollout_deep(int env_id, int n_hidden, const int* widths, c
                   stream);
 }
 
+// Workgroups (= trajectories) of mepol_rollout_deep itself the device holds at once: the
+// occupancy of the instance without a goal on this env, as mepol_rollout_deep_goal_plan_info
+// reports the goal instance's.
+extern "C" int mepol_rollout_deep_plan_info(int env_id, int n_hidden, const int* widths, int a_dim,
+                                            int* resident_workgroups) {
+  if (!resident_workgroups || !deep_shape_ok(env_id, n_hidden, widths, a_dim))
+    return deep_bad_args("mepol_rollout_deep_plan_info");
+  return env_id == 0 ? deep_resident<0, kGoalNone>(n_hidden, widths, resident_workgroups)
+                     : deep_resident<1, kGoalNone>(n_hidden, widths, resident_workgroups);
+}
+
 // mepol_rollout_deep on GridWorld with early termination at a goal: mepol_rollout_goal's episode
 // semantics and outputs for 3 to 6 hidden layers, one workgroup per trajectory (no error word is
 // ever set).  The workspace is mepol_rollout_deep_workspace_size's.

@@ -4,7 +4,11 @@
 //                that was rolled out in parallel: trajectories are taken in index order until the
 //                step budget is spent, the last one cut.  Integer arithmetic: any scan order gives
 //                the same result.
-//  gae           process_traj (:175-201) over ragged trajectories plus the concatenation of
+//  traj_cut      the episodes inside un-terminated rollouts: each trajectory is cut at the first
+//                step whose state a batched reward marked done, with the GOAL instances' zeros
+//                behind the end (goal_mode.hpp), so that any reward of the reached state samples
+//                on the one-launch rollouts.
+//  gae          process_traj (:175-201) over ragged trajectories plus the concatenation of
 //                :308-326: discounted targets, GAE advantages and the packed f64 states / actions.
 //                The two recurrences run backwards in f64, one lane per trajectory, every operation
 //                rounded on its own (_rn intrinsics: no contraction) in the reference's operator
@@ -66,6 +70,54 @@ __global__ __launch_bounds__(kBudgetThreads) void traj_budget_kernel(
     long long m = 0;
     for (int k = 0; k < kBudgetThreads; ++k) m += sused[k];
     meta[0] = m;
+  }
+}
+
+// ---- cut at the first done -----------------------------------------------------------------
+// One workgroup per trajectory (a grid-stride loop beyond kCutMaxBlocks of them).  Thread tid
+// scans steps tid, tid + 256, ... for its first non-zero done_step byte; the minimum over the
+// workgroup (the wave's xor butterfly, then the 4 waves through LDS: integers, any order) is the
+// episode's last step f, and all threads zero the three tails behind len = f + 1 with coalesced
+// stores, as goal_zero_tail (goal_mode.hpp) does for the GOAL instances.  Nothing in front of the
+// end is written, so kept rewards keep their bits.
+constexpr int kCutThreads = 256;
+constexpr int64_t kCutMaxBlocks = 1 << 20;
+
+__global__ __launch_bounds__(kCutThreads) void traj_cut_kernel(
+    const uint8_t* __restrict__ done_step, int64_t n, int64_t T, float* __restrict__ rewards,
+    float* __restrict__ states_rec, int nf, float* __restrict__ actions_rec, int a_dim,
+    int* __restrict__ len, int* __restrict__ done) {
+  __shared__ int sfirst[kCutThreads / kWave];
+  const int tid = threadIdx.x;
+  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint8_t* d = done_step + i * T;
+    int64_t first = T;  // T <= INT_MAX - 1
+    for (int64_t t = tid; t < T; t += kCutThreads) {
+      if (d[t] != 0) {
+        first = t;
+        break;
+      }
+    }
+    int f = (int)first;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) f = min(f, __shfl_xor(f, m, kWave));
+    if (lane_id() == 0) sfirst[tid / kWave] = f;
+    __syncthreads();
+    f = min(min(sfirst[0], sfirst[1]), min(sfirst[2], sfirst[3]));
+    __syncthreads();  // sfirst is rewritten by the next trajectory of this workgroup
+    const bool hit = f < T;
+    const int64_t L = hit ? (int64_t)f + 1 : T;
+    if (tid == 0) {
+      len[i] = (int)L;
+      done[i] = hit ? 1 : 0;
+    }
+    const int64_t rest = T - L;  // steps behind the end
+    float* s = states_rec + (i * (T + 1) + L + 1) * nf;
+    for (int64_t e = tid; e < rest * nf; e += kCutThreads) s[e] = 0.f;
+    float* a = actions_rec + (i * T + L) * a_dim;
+    for (int64_t e = tid; e < rest * a_dim; e += kCutThreads) a[e] = 0.f;
+    float* r = rewards + i * T + L;
+    for (int64_t e = tid; e < rest; e += kCutThreads) r[e] = 0.f;
   }
 }
 
@@ -232,6 +284,24 @@ extern "C" int mepol_traj_budget(const int32_t* len, const int32_t* done, int64_
   hipLaunchKernelGGL(traj_budget_kernel, dim3(1), dim3(kBudgetThreads), 0, (hipStream_t)stream,
                      len, done, (int)n, (long long)budget, len_out, done_out, (long long*)offsets,
                      (long long*)meta);
+  MEPOL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mepol_traj_cut(const uint8_t* done_step, int64_t n, int64_t T, float* rewards,
+                              float* states_rec, int num_features, float* actions_rec, int a_dim,
+                              int32_t* len, int32_t* done, void* stream) {
+  if (n == 0) return 0;
+  if (n < 0 || !done_step || !rewards || !states_rec || !actions_rec || !len || !done || T <= 0 ||
+      T > INT_MAX - 1 || num_features <= 0 || a_dim <= 0) {
+    set_error("mepol_traj_cut: bad arguments (null pointer, n < 0, T outside [1, 2^31 - 2], "
+              "num_features or a_dim < 1)");
+    return kErrBadArg;
+  }
+  const int64_t blocks = n < kCutMaxBlocks ? n : kCutMaxBlocks;
+  hipLaunchKernelGGL(traj_cut_kernel, dim3((unsigned)blocks), dim3(kCutThreads), 0,
+                     (hipStream_t)stream, done_step, n, T, rewards, states_rec, num_features,
+                     actions_rec, a_dim, len, done);
   MEPOL_CHECK_LAUNCH();
   return 0;
 }

@@ -21,6 +21,15 @@ for this env: the wall clips the position to exactly 0.45 with velocity 0 when i
 `position >= goal_position and velocity >= 0` is the same condition.  It samples on the one-launch
 threshold-goal rollouts.
 
+--env GridGoalAny and --env MountainCarLeft (build extensions) are goals the rollout kernels have
+no kind for.  GridGoalAny is the three reference GridWorld goals at once, AnyGoal(GridGoal((5,
+5)), GridGoal((2, 5)), GridGoal((5, 2))), with the GridGoal policy; MountainCarLeft is the left
+hilltop, BoxGoal((-inf, -inf), (-1.1, inf)): position <= -1.1, with MountainCarGoal's policy, so
+`mepol --env MountainCar` checkpoints load.  Both rewards are envs.BatchReward objects (a reward
+of the reached state alone, defined for whole batches), and so is any such reward of a user's:
+they sample on the un-terminated one-launch rollouts, cut at each trajectory's first done
+(algorithms/trpo.py).  A plain function reward keeps the reference's one-env host loop.
+
 MuJoCo goals (AntEscape, AntNavigate, AntJump, HumanoidUp) keep their specs but need mujoco-py,
 which is outside this build's scope.
 """
@@ -38,7 +47,9 @@ def build_parser():
     p = argparse.ArgumentParser(description="Goal-Based Reinforcement Learning - TRPO")
     p.add_argument("--num_workers", type=int, default=1,
                    help="How many parallel workers to use when collecting samples")
-    p.add_argument("--env", type=str, required=True, help="The MDP")
+    p.add_argument("--env", type=str, required=True,
+                   help="The MDP (build extensions: MountainCarGoal, GridGoalAny, "
+                        "MountainCarLeft)")
     p.add_argument("--policy_init", type=str, default=None,
                    help="Path to the weights for custom policy initialization.")
     p.add_argument("--num_epochs", type=int, required=True, help="The number of training epochs")
@@ -79,20 +90,29 @@ def checkpoint_widths(state_dict):
 
 
 def exp_specs():
-    from ..envs import (CustomRewardEnv, GridGoal, GridWorldContinuous, MountainCarContinuous,
-                        ThresholdGoal)
+    from ..envs import (AnyGoal, BoxGoal, CustomRewardEnv, GridGoal, GridWorldContinuous,
+                        MountainCarContinuous, ThresholdGoal)
 
-    def grid(goal):
-        return dict(env_create=lambda: CustomRewardEnv(GridWorldContinuous(), GridGoal(goal)),
+    def grid_reward(make_reward):
+        return dict(env_create=lambda: CustomRewardEnv(GridWorldContinuous(), make_reward()),
                     hidden_sizes=[300, 300], activation=nn.ReLU, log_std_init=-1.5)
 
+    def grid(goal):
+        return grid_reward(lambda: GridGoal(goal))
+
     # the MEPOL command line's MountainCar policy, so that its checkpoints load
-    mountain_car = dict(
-        env_create=lambda: CustomRewardEnv(MountainCarContinuous(), ThresholdGoal(0, 0.45)),
-        hidden_sizes=[300, 300], activation=nn.ReLU, log_std_init=-0.5)
+    def mountain_car_reward(make_reward):
+        return dict(env_create=lambda: CustomRewardEnv(MountainCarContinuous(), make_reward()),
+                    hidden_sizes=[300, 300], activation=nn.ReLU, log_std_init=-0.5)
+
+    mountain_car = mountain_car_reward(lambda: ThresholdGoal(0, 0.45))
+    inf = float("inf")
     mujoco = dict(env_create=None, hidden_sizes=[400, 300], activation=nn.ReLU, log_std_init=-0.5)
     return {"GridGoal1": grid((5, 5)), "GridGoal2": grid((2, 5)), "GridGoal3": grid((5, 2)),
             "MountainCarGoal": mountain_car,
+            "GridGoalAny": grid_reward(lambda: AnyGoal(GridGoal((5, 5)), GridGoal((2, 5)),
+                                                       GridGoal((5, 2)))),
+            "MountainCarLeft": mountain_car_reward(lambda: BoxGoal((-inf, -inf), (-1.1, inf))),
             "AntEscape": dict(mujoco), "AntNavigate": dict(mujoco), "AntJump": dict(mujoco),
             "HumanoidUp": dict(mujoco)}
 

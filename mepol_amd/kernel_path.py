@@ -1,8 +1,9 @@
 """What the Gaussian policy's HIP kernel path takes, and its layer chain, each written once for
 get_log_p (policy.py), the graph loop (algorithms/device_loop.py), TRPO's Fisher products
 (algorithms/trpo.py) and the one-launch rollouts (algorithms/mepol.py).  The gates stay with
-those consumers and add what only they know (row floors, dtypes, the optimizer); the gate of
-TRPO's goal sampler (goal_sampler) is here because it joins an env with a policy."""
+those consumers and add what only they know (row floors, dtypes, the optimizer); the gates of
+TRPO's samplers (goal_sampler, cut_sampler) are here because they join an env with a policy, and
+kernel_env, which says whether an env is the one the kernels step."""
 import os
 
 import torch
@@ -83,6 +84,29 @@ def hidden_backward(dz, x, Ws, hs, dW_out=None, db_out=None, dz_out=None, ws_wgr
     return dW, db
 
 
+MOUNTAINCAR, GRIDWORLD = 0, 1  # the kernels' env_id
+ENV_ACTIONS = (1, 2)           # action count of each
+
+
+def kernel_env(base):
+    """The kernels' env_id for `base`, MOUNTAINCAR (0) or GRIDWORLD (1), when it is exactly a
+    MountainCarContinuous or a GridWorldContinuous (no subclass) with the constants the HIP env
+    steps are compiled with (csrc/env_step.hpp), else None: every route that steps an env inside
+    a kernel asks this first."""
+    from .envs.gridworld import GridWorldContinuous
+    from .envs.mountain_car import MountainCarContinuous
+
+    if type(base) is GridWorldContinuous:
+        # the kernel's GridWorld is the default one: its size, step and walls are constants there
+        if (base.dim, base.max_delta, base.wall_width) == GRIDWORLD_DEFAULTS:
+            return GRIDWORLD
+    elif type(base) is MountainCarContinuous:
+        # and so are MountainCar's
+        if tuple(getattr(base, k) for k in MOUNTAINCAR_FIELDS) == MOUNTAINCAR_DEFAULTS:
+            return MOUNTAINCAR
+    return None
+
+
 def goal_sampler(env, policy):
     """(goal, layers) when TRPO's sampler (algorithms/trpo.py collect_sample_batch) takes a
     one-launch goal rollout, else None: an f64 policy on the GPU that
@@ -100,9 +124,6 @@ def goal_sampler(env, policy):
     ROLLOUT_DEEP_MAX_WORDS cap: that is where the deep kernel stops beating MEPOL's replayed
     per-step graph, and the sampler's only alternative is the host loop.
     MEPOL_TRPO_SAMPLER=host turns the kernel path off."""
-    from .algorithms.mepol import _rollout_layers, _rollout_mlp_layers
-    from .envs.gridworld import GridWorldContinuous
-    from .envs.mountain_car import MountainCarContinuous
     from .envs.wrappers import CustomRewardEnv, GridGoal, ThresholdGoal
 
     if os.environ.get("MEPOL_TRPO_SAMPLER", "kernel") == "host":
@@ -115,26 +136,50 @@ def goal_sampler(env, policy):
             return None
     elif not isinstance(goal, GridGoal):
         return None
-    if type(env.env) is GridWorldContinuous:
-        # the kernel's GridWorld is the default one: its size, step and walls are constants there
-        if (env.env.dim, env.env.max_delta, env.env.wall_width) != GRIDWORLD_DEFAULTS:
-            return None
-        a_dim = 2
-    elif type(env.env) is MountainCarContinuous and isinstance(goal, ThresholdGoal):
-        # and so are MountainCar's
-        if tuple(getattr(env.env, k) for k in MOUNTAINCAR_FIELDS) != MOUNTAINCAR_DEFAULTS:
-            return None
-        a_dim = 1
-    else:
+    env_id = kernel_env(env.env)
+    if env_id is None or (env_id == MOUNTAINCAR and not isinstance(goal, ThresholdGoal)):
         return None
+    layers = _sampler_layers(env, policy, env_id)
+    return None if layers is None else (goal, layers)
+
+
+def _sampler_layers(env, policy, env_id):
+    """The policy's layers as the one-launch rollouts take them (a tuple of two for
+    ops.rollout_mlp and the two-layer goal kernels, a list of 3 to 6 for the deep ones) when it is
+    an f64 policy on the GPU with the env's action count, else None: the policy half of
+    goal_sampler and cut_sampler."""
+    from .algorithms.mepol import _rollout_layers, _rollout_mlp_layers
+
+    a_dim = ENV_ACTIONS[env_id]
     log_std = getattr(policy, "log_std", None)
     if (log_std is None or not log_std.is_cuda or log_std.dtype != torch.float64
             or getattr(policy, "action_dim", None) != a_dim
             or policy.mean.weight.dtype != torch.float64):
         return None
-    layers = (_rollout_mlp_layers(policy, env.num_features, a_dim)
-              or _rollout_layers(policy, env.num_features, a_dim, deep=True, word_cap=False))
-    return None if layers is None else (goal, layers)
+    return (_rollout_mlp_layers(policy, env.num_features, a_dim)
+            or _rollout_layers(policy, env.num_features, a_dim, deep=True, word_cap=False))
+
+
+def cut_sampler(env, policy):
+    """(reward, layers, env_id) when TRPO's sampler takes the "roll out, then cut" route, else
+    None: a CustomRewardEnv directly over an env kernel_env accepts, whose reward is a
+    BatchReward (envs/wrappers.py: a function of the reached state alone, defined for batches),
+    and a policy as goal_sampler takes it.  A round is then an UN-terminated one-launch rollout
+    (ops.rollout_mlp / ops.rollout_deep), one reward.batch call over its recorded states and
+    ops.traj_cut.  It serves every goal the in-kernel kinds do not cover; GridGoal and
+    ThresholdGoal are no BatchReward and keep goal_sampler's route, which is tried first.
+    MEPOL_TRPO_SAMPLER=host turns this route off too."""
+    from .envs.wrappers import BatchReward, CustomRewardEnv
+
+    if os.environ.get("MEPOL_TRPO_SAMPLER", "kernel") == "host":
+        return None
+    if type(env) is not CustomRewardEnv or not isinstance(env.get_reward, BatchReward):
+        return None
+    env_id = kernel_env(env.env)
+    if env_id is None:
+        return None
+    layers = _sampler_layers(env, policy, env_id)
+    return None if layers is None else (env.get_reward, layers, env_id)
 
 
 def critic_fit_refusal(vfunc, vfunc_optimizer, states, critic_batch_size):

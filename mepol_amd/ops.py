@@ -896,6 +896,15 @@ def rollout_mlp_plan(n, h0, h1, a_dim):
     return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
 
 
+def rollout_deep_plan(env_id, widths, a_dim):
+    """{"resident_workgroups"}: trajectories of rollout_deep itself (the instance without a goal
+    on this env) the device holds at once for hidden layers of these widths."""
+    wg = ctypes.c_int()
+    arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
+    call("mepol_rollout_deep_plan_info", env_id, len(widths), arr, a_dim, ctypes.byref(wg))
+    return {"resident_workgroups": wg.value}
+
+
 def rollout_goal_plan(n, h0, h1, a_dim=2):
     """rollout_mlp_plan for rollout_goal: the form the goal-mode kernel's own occupancy gives."""
     wg, kc = ctypes.c_int(), ctypes.c_int()
@@ -1149,6 +1158,36 @@ def traj_budget(lens, dones, budget):
     call("mepol_traj_budget", ptr(lens.contiguous()), ptr(dones.contiguous()), n, int(budget),
          ptr(len_out), ptr(done_out), ptr(offsets), ptr(meta), _stream())
     return len_out, done_out, offsets, meta
+
+
+def traj_cut(done_step, rewards, states_rec, actions_rec):
+    """The episodes inside un-terminated rollouts (mepol_traj_cut): every trajectory is cut at its
+    first step t with done_step[i, t] set, IN PLACE.  done_step [n,T] bool or uint8 (any non-zero
+    byte), rewards [n,T] f32, states_rec [n,T+1,nf] f32, actions_rec [n,T,a] f32, all contiguous on
+    the device: rewards[i, len:], actions_rec[i, len:] and states_rec[i, len + 1:] become +0.0,
+    everything before keeps its bits.  Returns (lens int32 [n], dones int32 [n]): len = t + 1 and
+    done = 1 at a first hit, else len = T and done = 0 -- what the goal rollouts write."""
+    _require_device(done_step, rewards, states_rec, actions_rec)
+    if rewards.dim() != 2 or states_rec.dim() != 3 or actions_rec.dim() != 3:
+        raise ValueError("traj_cut: rewards [n,T], states_rec [n,T+1,nf], actions_rec [n,T,a]")
+    n, T = rewards.shape
+    nf, a = states_rec.shape[2], actions_rec.shape[2]
+    if (tuple(done_step.shape) != (n, T) or tuple(states_rec.shape) != (n, T + 1, nf)
+            or tuple(actions_rec.shape) != (n, T, a)):
+        raise ValueError("traj_cut: tensor shapes do not fit the batch")
+    if (done_step.dtype not in (torch.bool, torch.uint8) or rewards.dtype != torch.float32
+            or states_rec.dtype != torch.float32 or actions_rec.dtype != torch.float32):
+        raise ValueError("traj_cut: bool or uint8 done_step, f32 rewards / records")
+    if not all(t.is_contiguous() for t in (done_step, rewards, states_rec, actions_rec)):
+        raise ValueError("traj_cut: contiguous tensors are needed (the records are cut in place)")
+    if len({t.device for t in (done_step, rewards, states_rec, actions_rec)}) != 1:
+        raise ValueError("traj_cut: tensors on one device")
+    dev = rewards.device
+    lens = torch.empty(n, dtype=torch.int32, device=dev)
+    dones = torch.empty(n, dtype=torch.int32, device=dev)
+    call("mepol_traj_cut", ptr(done_step), n, T, ptr(rewards), ptr(states_rec), nf,
+         ptr(actions_rec), a, ptr(lens), ptr(dones), _stream())
+    return lens, dones
 
 
 def gae(rewards, values, lens, dones, offsets, n_out, gamma, lambd, states_rec, actions_rec):

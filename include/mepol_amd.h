@@ -37,7 +37,9 @@ extern "C" {
  * trajectory sums).  Additions keep the number: the *_plan_info queries, mepol_critic_fit with
  * mepol_critic_fit_plan_info, mepol_rollout_deep_goal with
  * mepol_rollout_deep_goal_plan_info, the five mepol_rollout_*goal_threshold* entry points,
- * mepol_traj_cut and mepol_rollout_deep_plan_info came in at 4.  mepol_abi_version() returns the library's value. */
+ * mepol_traj_cut, mepol_rollout_deep_plan_info and the box-maze entry points (mepol_maze,
+ * mepol_step_maze, mepol_rollout_step_maze, mepol_rollout_maze*, mepol_rollout_deep_maze*) came
+ * in at 4.  mepol_abi_version() returns the library's value. */
 #define MEPOL_ABI_VERSION 4
 
 #define MEPOL_ERR_BAD_ARG 1001
@@ -657,6 +659,72 @@ int mepol_critic_fit(const double* states, const double* targets, int64_t n, con
                      int64_t n_steps, int batch, int nf, int h0, int h1, double* const* params,
                      double* const* exp_avg, double* const* exp_avg_sq, const double* scal,
                      double beta1, double beta2, double eps, double* loss_out, void* stream);
+
+/* ---- box mazes (mepol_amd/envs/maze.py BoxMazeContinuous) ----------------------------------------
+ * A 2-D continuous maze whose bounds, step size and axis-aligned wall boxes are data: GridWorld's
+ * step (src/envs/gridworld_continuous.py:128-154) with its constants made arguments, in the same
+ * IEEE order.  Configured as the default GridWorld it gives the bits of the env_id 1 entry points.
+ * The state is f32 [n, 2], the action count is 2.  A move is undone when its landing point lies in
+ * any of the first n_walls closed boxes (x0, x1, y0, y1), then when it lies on or outside a bound.
+ *
+ * The maze entry points are the env_id 1 ones folded by goal kind: MEPOL_GOAL_NONE is
+ * mepol_rollout_mlp / mepol_rollout_deep (visited and final_state may be given, the goal arguments
+ * and rewards_rec / len_out / done_out are ignored and may be 0 / NULL); MEPOL_GOAL_BALL is
+ * mepol_rollout_goal / mepol_rollout_deep_goal with (goal_x, goal_y) and goal_value = radius >= 0;
+ * MEPOL_GOAL_THRESHOLD is mepol_rollout_goal_threshold / mepol_rollout_deep_goal_threshold with
+ * coord 0 or 1 and goal_value = threshold (not NaN).  Outputs, workspace layout, error word and
+ * summation order are those of the calls they fold; the plan and workspace queries ask the
+ * occupancy of the maze instance of that goal kind.  The existing entry points keep rejecting
+ * env_id 2.  MEPOL_ERR_BAD_ARG, with a message, for a NULL maze, n_walls outside
+ * 0 .. MEPOL_MAZE_MAX_WALLS, a bound, max_delta or used wall number that is not finite, an
+ * inverted wall box (x0 > x1 or y0 > y1), inverted bounds (lo >= hi), a_dim != 2, and whatever
+ * the folded call rejects. */
+#define MEPOL_MAZE_MAX_WALLS 16
+typedef struct mepol_maze {
+  double xlo, xhi, ylo, yhi; /* open bounds */
+  double max_delta;          /* each action coordinate is clipped to +-max_delta */
+  int32_t n_walls;           /* walls in use, 0 .. MEPOL_MAZE_MAX_WALLS */
+  int32_t reserved;          /* 0 */
+  double walls[MEPOL_MAZE_MAX_WALLS][4]; /* (x0, x1, y0, y1), closed boxes */
+} mepol_maze;
+
+#define MEPOL_GOAL_NONE 0
+#define MEPOL_GOAL_BALL 1
+#define MEPOL_GOAL_THRESHOLD 2
+
+/* mepol_step_gridworld and mepol_rollout_step on a maze. */
+int mepol_step_maze(const mepol_maze* maze, float* state, const double* action, int64_t n,
+                    void* stream);
+int mepol_rollout_step_maze(const mepol_maze* maze, float* env_f32, const double* mean,
+                            const double* noise, const double* log_std, int64_t n, int a_dim,
+                            int64_t t, int64_t T, float* states_rec, float* actions_rec,
+                            double* policy_in, void* stream);
+/* The two-layer one-launch rollout on a maze, in both of its forms. */
+int mepol_rollout_maze_workspace_size(int goal_kind, int64_t n, int64_t T, int h0, int h1,
+                                      int a_dim, size_t* bytes);
+int mepol_rollout_maze_plan_info(int goal_kind, int64_t n, int h0, int h1, int a_dim,
+                                 int* workgroups_per_traj, int* k_chunks);
+int mepol_rollout_maze(const mepol_maze* maze, int goal_kind, const double* W1, const double* b1,
+                       int h0, const double* W2t, const double* b2, int h1, const double* Wm,
+                       const double* bm, const double* log_std, int a_dim, const float* init32,
+                       const double* noise, int64_t n, int64_t T, float goal_x, float goal_y,
+                       int coord, double goal_value, float* states_rec, float* actions_rec,
+                       double* visited, double* final_state, float* rewards_rec, int32_t* len_out,
+                       int32_t* done_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The 3-to-6-layer one-launch rollout on a maze. */
+int mepol_rollout_deep_maze_workspace_size(int64_t n, int64_t T, int n_hidden, const int* widths,
+                                           int a_dim, size_t* bytes);
+int mepol_rollout_deep_maze_plan_info(int goal_kind, int n_hidden, const int* widths, int a_dim,
+                                      int* resident_workgroups);
+int mepol_rollout_deep_maze(const mepol_maze* maze, int goal_kind, int n_hidden, const int* widths,
+                            const double* W1, const double* b1, const double* Wt, const double* bt,
+                            const double* Wm, const double* bm, const double* log_std, int a_dim,
+                            const float* init32, const double* noise, int64_t n, int64_t T,
+                            float goal_x, float goal_y, int coord, double goal_value,
+                            float* states_rec, float* actions_rec, double* visited,
+                            double* final_state, float* rewards_rec, int32_t* len_out,
+                            int32_t* done_out, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,20 @@ _c_sz = ctypes.c_size_t
 _c_vp = ctypes.c_void_p
 
 ABI_VERSION = 4  # include/mepol_amd.h MEPOL_ABI_VERSION
+MAZE_MAX_WALLS = 16  # MEPOL_MAZE_MAX_WALLS
+GOAL_NONE, GOAL_BALL, GOAL_THRESHOLD = 0, 1, 2  # MEPOL_GOAL_*
+
+
+class Maze(ctypes.Structure):
+    """mepol_maze: the box maze the env 2 entry points take by pointer."""
+    _fields_ = [("xlo", _c_dbl), ("xhi", _c_dbl), ("ylo", _c_dbl), ("yhi", _c_dbl),
+                ("max_delta", _c_dbl), ("n_walls", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("walls", (_c_dbl * 4) * MAZE_MAX_WALLS)]
+
+
+_c_mp = ctypes.POINTER(Maze)
+_c_flt = ctypes.c_float
+_c_ip = ctypes.POINTER(_c_int)
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
 SIGNATURES = {
@@ -143,6 +157,23 @@ SIGNATURES = {
                                           _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp],
     "mepol_rollout_deep_goal_threshold_plan_info": [_c_int, _c_int, ctypes.POINTER(_c_int), _c_int,
                                                     ctypes.POINTER(_c_int)],
+    "mepol_step_maze": [_c_mp, _c_vp, _c_vp, _c_i64, _c_vp],
+    "mepol_rollout_step_maze": [_c_mp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_i64, _c_i64,
+                                _c_vp, _c_vp, _c_vp, _c_vp],
+    "mepol_rollout_maze_workspace_size": [_c_int, _c_i64, _c_i64, _c_int, _c_int, _c_int,
+                                          ctypes.POINTER(_c_sz)],
+    "mepol_rollout_maze_plan_info": [_c_int, _c_i64, _c_int, _c_int, _c_int, _c_ip, _c_ip],
+    "mepol_rollout_maze": [_c_mp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
+                           _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_flt, _c_flt, _c_int,
+                           _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz,
+                           _c_vp],
+    "mepol_rollout_deep_maze_workspace_size": [_c_i64, _c_i64, _c_int, _c_ip, _c_int,
+                                               ctypes.POINTER(_c_sz)],
+    "mepol_rollout_deep_maze_plan_info": [_c_int, _c_int, _c_ip, _c_int, _c_ip],
+    "mepol_rollout_deep_maze": [_c_mp, _c_int, _c_int, _c_ip, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_i64, _c_flt, _c_flt,
+                                _c_int, _c_dbl, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                _c_vp, _c_sz, _c_vp],
     "mepol_traj_budget": [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],
     "mepol_traj_cut": [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_vp,
                        _c_vp],

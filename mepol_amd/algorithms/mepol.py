@@ -50,8 +50,10 @@ class _RolloutGraph:
     and replayed every epoch; the policy's parameters are read in place, so load_state_dict
     between epochs needs no re-capture."""
 
-    def __init__(self, key, policy, env_id, init, T, a_dim, nf):
+    def __init__(self, key, policy, env_id, init, T, a_dim, nf, maze=None):
         dev = init.device
+        # the box maze's struct (env_id 2), built once: the captured launches copy it by value
+        self.maze = ops.maze_struct(maze) if maze is not None else None
         n = init.shape[0]
         self.key = key  # _rollout_graph's: what this capture is valid for
         self.init = init.clone()
@@ -82,11 +84,11 @@ class _RolloutGraph:
         self.policy_in.copy_(self.init)
         self.states[:, 0].copy_(self.init)
         e64 = self.env if self.env_id == 0 else None
-        e32 = self.env if self.env_id == 1 else None
+        e32 = self.env if self.env_id != 0 else None
         for t in range(steps):
             mean = self._policy().mean_action(self.policy_in).contiguous()
             ops.rollout_step(self.env_id, e64, e32, mean, self.noise[t], self.log_std, t, self.T,
-                             self.states, self.actions, self.policy_in)
+                             self.states, self.actions, self.policy_in, maze=self.maze)
 
     def run(self, init, noise):
         self.init.copy_(init)
@@ -121,16 +123,18 @@ def _release_graphs_at_exit():
         par.release_graphs()
 
 
-def _rollout_graph(policy, env_id, init, T, a_dim, nf):
+def _rollout_graph(policy, env_id, init, T, a_dim, nf, maze=None):
     if os.environ.get("MEPOL_ROLLOUT_GRAPH", "1") == "0" or not policy.log_std.is_contiguous():
         return None
-    key = (env_id, init.shape[0], T, a_dim, nf, tuple(p.data_ptr() for p in policy.parameters()))
+    # a maze's layout is baked into the captured launches: it is part of the key
+    key = (env_id, init.shape[0], T, a_dim, nf, tuple(p.data_ptr() for p in policy.parameters()),
+           maze.kernel_key() if maze is not None else None)
     per = _ROLLOUT_GRAPHS.setdefault(policy, {})
     g = per.get(key)
     if g is None:
         if len(per) >= 4:  # bounded: the epoch and full-entropy shapes of a run
             per.clear()
-        g = per[key] = _RolloutGraph(key, policy, env_id, init, T, a_dim, nf)
+        g = per[key] = _RolloutGraph(key, policy, env_id, init, T, a_dim, nf, maze=maze)
     return g
 
 
@@ -184,8 +188,8 @@ def collect_particles_device(env, policy, num_traj, traj_len, state_filter, gene
 
     Returns device tensors: states f32 [nt, T+1, nf], actions f32 [nt, T, a], real lengths
     int32 [nt, 1], next_states f32 [N, ns] (particle p = n*T + t <-> s_{n, t+1}, mepol.py:98-109).
-    MountainCar / GridWorld with the kernels' constants (kernel_path.kernel_env) step in a HIP
-    kernel (one fused launch per step after the MLP, or all steps in one launch);
+    MountainCar / GridWorld with the kernels' constants and any BoxMazeContinuous
+    (kernel_path.kernel_env) step in a HIP kernel (one fused launch per step after the MLP, or all steps in one launch);
     any other env is stepped on the host in lockstep with one batched policy call per step.
     `visited` (optional, f64 [nt, T, nf]) receives the env's own state after every step (f64
     MountainCar state / GridWorld f32 state, not the f32 particle copy), for the heatmap.
@@ -230,7 +234,8 @@ def collect_particles_device(env, policy, num_traj, traj_len, state_filter, gene
 
 
 def _rollout_hip_stepped(env_id, base, policy, total, lo, hi, generator, visited, states, actions):
-    """Trajectories [lo, hi) of `total` on a HIP-stepped env (0 MountainCar, 1 GridWorld) by the
+    """Trajectories [lo, hi) of `total` on a HIP-stepped env (0 MountainCar, 1 GridWorld, 2 a box
+    maze, whose layout `base` goes along as the kernels' maze argument) by the
     first route that takes the policy: the two-layer one-launch kernel, the deep one, the replayed
     per-step graph (not with `visited`), the eager per-step loop.  All `total` initial states, then
     all the noise, are drawn first.  Returns the given tensors filled, or the graph's copies."""
@@ -240,6 +245,7 @@ def _rollout_hip_stepped(env_id, base, policy, total, lo, hi, generator, visited
     init = base.reset_batch_torch(total, dev, generator)[lo:hi]
     noise = torch.randn((T, total, a_dim), dtype=torch.float64, device=dev,
                         generator=generator)[:, lo:hi]
+    maze = kernel_path.maze_of(base, env_id)
     layers = _rollout_mlp_layers(policy, nf, a_dim) or _rollout_deep_layers(policy, nf, a_dim)
     if layers:
         # all T steps in one launch (csrc/envs.hip rollout_mlp_kernel, or csrc/rollout_deep.hip
@@ -247,22 +253,24 @@ def _rollout_hip_stepped(env_id, base, policy, total, lo, hi, generator, visited
         head = (policy.mean.weight.detach(), policy.mean.bias.detach(), policy.log_std.detach(),
                 init, noise, states, actions, visited)
         if len(layers) == 2:
-            ops.rollout_mlp(env_id, *layers[0], *layers[1], *head)
+            ops.rollout_mlp(env_id, *layers[0], *layers[1], *head, maze=maze)
         else:
-            ops.rollout_deep(env_id, layers, *head)
+            ops.rollout_deep(env_id, layers, *head, maze=maze)
         return states, actions
-    graph = _rollout_graph(policy, env_id, init, T, a_dim, nf) if visited is None else None
+    graph = (_rollout_graph(policy, env_id, init, T, a_dim, nf, maze=maze) if visited is None
+             else None)
     if graph is not None:
         return graph.run(init, noise)
     env64 = init.clone() if env_id == 0 else None
-    env32 = init.clone() if env_id == 1 else None
+    env32 = init.clone() if env_id != 0 else None
+    maze = ops.maze_struct(maze) if maze is not None else None
     policy_in = init.to(torch.float64).contiguous()
     states[:, 0] = init.to(torch.float32)
     log_std = policy.log_std.detach().contiguous()
     for t in range(T):
         mean = policy.mean_action(policy_in).contiguous()
         ops.rollout_step(env_id, env64, env32, mean, noise[t], log_std, t, T, states, actions,
-                         policy_in)
+                         policy_in, maze=maze)
         if visited is not None:
             visited[:, t].copy_(policy_in)
     return states, actions

@@ -381,6 +381,7 @@ _ROUND_CAPACITY = {}
 BALL, THRESHOLD = "ball", "threshold"  # the goal kinds of the rollout kernels
 CUT = "cut"                            # no goal in the kernel: the un-terminated rollouts
 MOUNTAINCAR, GRIDWORLD = kernel_path.MOUNTAINCAR, kernel_path.GRIDWORLD  # their env_id
+MAZE = kernel_path.MAZE
 
 
 def _round_capacity(h0, h1, a_dim, device, env_id=GRIDWORLD, kind=BALL):
@@ -393,8 +394,8 @@ def _round_capacity(h0, h1, a_dim, device, env_id=GRIDWORLD, kind=BALL):
     key = (h0, h1, a_dim, device, os.environ.get("MEPOL_ROLLOUT_MW"), env_id, kind)
     if key not in _ROUND_CAPACITY:
         def multi(n):
-            plan = (ops.rollout_goal_plan(n, h0, h1, a_dim) if kind == BALL
-                    else ops.rollout_mlp_plan(n, h0, h1, a_dim) if kind == CUT
+            plan = (ops.rollout_goal_plan(n, h0, h1, a_dim, env_id=env_id) if kind == BALL
+                    else ops.rollout_mlp_plan(n, h0, h1, a_dim, env_id=env_id) if kind == CUT
                     else ops.rollout_goal_threshold_plan(env_id, n, h0, h1, a_dim))
             return plan["workgroups_per_traj"] > 1
 
@@ -414,7 +415,7 @@ def _round_capacity_deep(widths, a_dim, device, env_id=GRIDWORLD, kind=BALL):
     resident rows set the kernel's LDS, so its occupancy)."""
     key = (tuple(widths), a_dim, device, os.environ.get("MEPOL_ROLLOUT_KL"), env_id, kind)
     if key not in _ROUND_CAPACITY:
-        plan = (ops.rollout_deep_goal_plan(widths, a_dim) if kind == BALL
+        plan = (ops.rollout_deep_goal_plan(widths, a_dim, env_id=env_id) if kind == BALL
                 else ops.rollout_deep_plan(env_id, widths, a_dim) if kind == CUT
                 else ops.rollout_deep_goal_threshold_plan(env_id, widths, a_dim))
         _ROUND_CAPACITY[key] = max(plan["resident_workgroups"], 1)
@@ -429,11 +430,11 @@ def _draw_round(base, R, T, a_dim, device, generator):
     return init, noise
 
 
-def _goal_round(goal, layers, head, env_id):
+def _goal_round(goal, layers, head, env_id, maze=None):
     """(fill, cap kind) of the in-kernel goal route: fill(init, noise, states, actions, rewards)
     runs one round on the GOAL instance of env x goal kind (kernel_path.goal_sampler admits no
     other pair) and returns (lens, dones, err, rerun), the last two None for the deep rollouts,
-    which have no error word and so no re-run."""
+    which have no error word and so no re-run.  maze: the box maze's struct for env_id 2."""
     deep = len(layers) > 2
     kind = THRESHOLD if isinstance(goal, ThresholdGoal) else BALL
     test = (goal.goal, goal.radius) if kind == BALL else (goal.index, goal.threshold)
@@ -445,26 +446,28 @@ def _goal_round(goal, layers, head, env_id):
         roll = (*head, init, noise, *test, states, actions, rewards, lens, dones)
         if deep:
             if kind == BALL:
-                ops.rollout_deep_goal(layers, *roll)
+                ops.rollout_deep_goal(layers, *roll, env_id=env_id, maze=maze)
             else:
-                ops.rollout_deep_goal_threshold(env_id, layers, *roll)
+                ops.rollout_deep_goal_threshold(env_id, layers, *roll, maze=maze)
             return lens, dones, None, None
         (W1, b1), (W2, b2) = layers
         if kind == BALL:
-            err, rerun = ops.rollout_goal(W1, b1, W2, b2, *roll, defer_check=True)
+            err, rerun = ops.rollout_goal(W1, b1, W2, b2, *roll, env_id=env_id,
+                                          defer_check=True, maze=maze)
         else:
             err, rerun = ops.rollout_goal_threshold(env_id, W1, b1, W2, b2, *roll,
-                                                    defer_check=True)
+                                                    defer_check=True, maze=maze)
         return lens, dones, err, rerun
 
     return fill, kind
 
 
-def _cut_round(goal, layers, head, env_id):
+def _cut_round(goal, layers, head, env_id, maze=None):
     """(fill, cap kind) of the "roll out, then cut" route (kernel_path.cut_sampler): fill rolls
     the round out UN-terminated in one launch (ops.rollout_mlp, which handles its own error word,
     or ops.rollout_deep), evaluates the BatchReward once over the env's own state after every
-    step (MountainCar's f64 `visited`; GridWorld's f32 records widened, which is exact) and cuts
+    step (MountainCar's f64 `visited`; GridWorld's and the maze's f32 records widened, which is
+    exact) and cuts
     every trajectory at its first done (ops.traj_cut): the outputs of a goal-mode rollout."""
     deep = len(layers) > 2
     who = type(goal).__name__
@@ -474,10 +477,11 @@ def _cut_round(goal, layers, head, env_id):
         visited = (torch.empty((R, T, 2), dtype=torch.float64, device=init.device)
                    if env_id == MOUNTAINCAR else None)
         if deep:
-            ops.rollout_deep(env_id, layers, *head, init, noise, states, actions, visited=visited)
+            ops.rollout_deep(env_id, layers, *head, init, noise, states, actions, visited=visited,
+                             maze=maze)
         else:
             ops.rollout_mlp(env_id, *layers[0], *layers[1], *head, init, noise, states, actions,
-                            visited=visited)
+                            visited=visited, maze=maze)
         env_states = visited if visited is not None else states[:, 1:].to(torch.float64)
         out = goal.batch(env_states)
         if not (isinstance(out, tuple) and len(out) == 2 and all(torch.is_tensor(x) for x in out)):
@@ -509,7 +513,9 @@ def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, r
     env_id = kernel_path.kernel_env(base) if cut_env is None else cut_env
     widths = [W.shape[0] for W, _ in layers]
     head = (policy.mean.weight.detach(), policy.mean.bias.detach(), policy.log_std.detach())
-    fill, kind = (_goal_round if cut_env is None else _cut_round)(goal, layers, head, env_id)
+    maze = kernel_path.maze_of(base, env_id)
+    maze = ops.maze_struct(maze) if maze is not None else None
+    fill, kind = (_goal_round if cut_env is None else _cut_round)(goal, layers, head, env_id, maze)
     # the occupancy of the instance that runs
     cap = (_round_capacity_deep(widths, a_dim, dev, env_id, kind) if len(layers) > 2
            else _round_capacity(*widths, a_dim, dev, env_id, kind))
@@ -523,7 +529,7 @@ def _collect_kernel(env, policy, goal, layers, batch_size, T, generator, draw, r
         states = torch.empty((R, T + 1, 2), dtype=torch.float32, device=dev)
         actions = torch.empty((R, T, a_dim), dtype=torch.float32, device=dev)
         rewards = torch.empty((R, T), dtype=torch.float32, device=dev)
-        if env_id == GRIDWORLD:
+        if env_id != MOUNTAINCAR:
             init = init.to(torch.float32)
         lens, dones, err, rerun = fill(init, noise, states, actions, rewards)
         kept_len, kept_done, _, meta = ops.traj_budget(lens, dones, remaining)

@@ -5,6 +5,9 @@
 //                State is f64 (np.array([position, velocity]), :44).
 //  GridWorld     src/envs/gridworld_continuous.py:128-154, walls :66-76.  State is f32
 //                (:150); the move is evaluated in f64 (f32 state + f64 clipped action).
+//  Box maze      mepol_amd/envs/maze.py (no counterpart in the reference): GridWorld's step with
+//                bounds, max_delta and up to 16 wall boxes as data, a kernel argument of the
+//                ENV = 2 instances (env_step.hpp Maze::step, MazeArgs).
 //  ErgodicEnv    src/envs/wrappers.py:12-15: done is always False, every trajectory runs T steps.
 //
 // Each step is evaluated with the same IEEE operations, in the same order, as the reference's
@@ -40,17 +43,28 @@ __global__ void step_gw_kernel(float* __restrict__ s, const double* __restrict__
   s[2 * i + 1] = y;
 }
 
+__global__ void step_maze_kernel(float* __restrict__ s, const double* __restrict__ a, int64_t n,
+                                 MazeArgs mz) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float x = s[2 * i], y = s[2 * i + 1];
+  Maze::step(x, y, a[2 * i], a[2 * i + 1], mz);
+  s[2 * i] = x;
+  s[2 * i + 1] = y;
+}
+
 // One rollout step for n trajectories.  env_f64: MountainCar state [n,2] (f64);
-// env_f32: GridWorld state [n,2] (f32).  policy_in [n,2] f64 receives the next policy input.
-// states_rec [n, T+1, 2] f32, actions_rec [n, T, a_dim] f32.
-template <int ENV>
+// env_f32: GridWorld / maze state [n,2] (f32).  policy_in [n,2] f64 receives the next policy input.
+// states_rec [n, T+1, 2] f32, actions_rec [n, T, a_dim] f32.  MZ: MazeArgs for ENV 2, else empty
+// (grid_step, env_step.hpp).
+template <int ENV, typename... MZ>
 __global__ void rollout_step_kernel(double* __restrict__ env_f64, float* __restrict__ env_f32,
                                     const double* __restrict__ mean,
                                     const double* __restrict__ noise,
                                     const double* __restrict__ log_std, int64_t n, int a_dim,
                                     int64_t t, int64_t T, float* __restrict__ states_rec,
                                     float* __restrict__ actions_rec,
-                                    double* __restrict__ policy_in) {
+                                    double* __restrict__ policy_in, MZ... mz) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   double act[8];
@@ -59,7 +73,7 @@ __global__ void rollout_step_kernel(double* __restrict__ env_f64, float* __restr
     act[j] = __dadd_rn(mean[i * a_dim + j], __dmul_rn(noise[i * a_dim + j], exp(log_std[j])));
     actions_rec[(i * T + t) * a_dim + j] = (float)act[j];
   }
-  if (ENV == 0) {
+  if constexpr (ENV == 0) {
     double p = env_f64[2 * i], v = env_f64[2 * i + 1];
     MountainCar::step(p, v, act[0]);
     env_f64[2 * i] = p;
@@ -70,7 +84,7 @@ __global__ void rollout_step_kernel(double* __restrict__ env_f64, float* __restr
     states_rec[(i * (T + 1) + t + 1) * 2 + 1] = (float)v;
   } else {
     float x = env_f32[2 * i], y = env_f32[2 * i + 1];
-    GridWorld::step(x, y, act[0], act[1]);
+    grid_step<ENV>(x, y, act[0], act[1], mz...);
     env_f32[2 * i] = x;
     env_f32[2 * i + 1] = y;
     policy_in[2 * i] = (double)x;
@@ -101,9 +115,9 @@ constexpr unsigned long long kMailEmpty = ~0ull;
 constexpr int kRollMaxA = 8;
 constexpr int kRollChunks = 4;
 
-// Goal mode (GOAL = kGoalBall, GridWorld only, or kGoalThreshold, either env): GoalArgs, goal_test
-// and goal_zero_tail of goal_mode.hpp.
-template <int ENV, int U, int GOAL = kGoalNone>
+// Goal mode (GOAL = kGoalBall, GridWorld and the maze, or kGoalThreshold, any env): GoalArgs,
+// goal_test and goal_zero_tail of goal_mode.hpp.  MZ: MazeArgs for ENV 2, else empty (grid_step).
+template <int ENV, int U, int GOAL = kGoalNone, typename... MZ>
 __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, int h0,
     const double* __restrict__ W2t, const double* __restrict__ b2, int h1,
@@ -111,8 +125,9 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     const double* __restrict__ log_std, int a_dim, const double* __restrict__ init64,
     const float* __restrict__ init32, const double* __restrict__ noise, int64_t n, int64_t T,
     float* __restrict__ states_rec, float* __restrict__ actions_rec,
-    double* __restrict__ visited, double* __restrict__ final_state, int KL, GoalArgs goal) {
-  static_assert(GOAL != kGoalBall || ENV == 1, "the ball goal is GridWorld's");
+    double* __restrict__ visited, double* __restrict__ final_state, int KL, GoalArgs goal,
+    MZ... mz) {
+  static_assert(GOAL != kGoalBall || ENV != 0, "the ball goal needs an f32-state env");
   extern __shared__ double sW2[];  // [KL][blockDim.x]: W2^T rows 0 .. KL - 1
   __shared__ double sx[2];
   __shared__ int sgoal;  // GOAL: the step just taken reached the goal (thread 0 writes it)
@@ -218,12 +233,12 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
       }
       if (t + 1 < T)
         for (int a = 0; a < a_dim; ++a) nz[a] = nz_next[a];
-      if (ENV == 0) {
+      if constexpr (ENV == 0) {
         MountainCar::step(p, v, act[0]);
         sx[0] = p;
         sx[1] = v;
       } else {
-        GridWorld::step(gx, gy, act[0], act[1]);
+        grid_step<ENV>(gx, gy, act[0], act[1], mz...);
         sx[0] = (double)gx;
         sx[1] = (double)gy;
       }
@@ -280,7 +295,8 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
 // PROBE (tools/variants/rollout_probe.hip only): thread 0 of each workgroup accumulates
 // s_memtime spans of the step's phases into probe[blockIdx.x][8]; the product has PROBE = false.
 constexpr int kRollMwWaves = kRollChunks;  // one layer-2 chain per wave
-template <int ENV, bool PROBE = false, int GOAL = kGoalNone>
+// MZ: MazeArgs for ENV 2, else empty (grid_step); every thread of every part reads the same one.
+template <int ENV, bool PROBE = false, int GOAL = kGoalNone, typename... MZ>
 __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, int h0,
     const double* __restrict__ W2t, const double* __restrict__ b2, int h1,
@@ -290,8 +306,8 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     float* __restrict__ states_rec, float* __restrict__ actions_rec,
     double* __restrict__ visited, double* __restrict__ final_state, int np, int nw,
     unsigned long long* __restrict__ mail, int* __restrict__ err, int* __restrict__ ticket,
-    long long* __restrict__ probe, GoalArgs goal) {
-  static_assert(GOAL != kGoalBall || ENV == 1, "the ball goal is GridWorld's");
+    long long* __restrict__ probe, GoalArgs goal, MZ... mz) {
+  static_assert(GOAL != kGoalBall || ENV != 0, "the ball goal needs an f32-state env");
   extern __shared__ double sW2[];  // [h0][64]: W2^T rows, this part's 64 columns
   __shared__ double sh1[kRollMaxH];
   __shared__ double spart[kRollMwWaves][64];
@@ -327,6 +343,7 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
   // bits: each is stepped by the same instruction sequence (MountainCar::step, its cos()
   // included, or GridWorld::step) on the same action, the part-ordered sum of the same mail
   // words.  Keep the env step and the hit test free of anything that differs between parts.
+  // (The maze's walls are a kernel argument: the same bytes in every part.)
   __shared__ int sticket;
   if (threadIdx.x == 0) sticket = atomicAdd(ticket, 1);
   __syncthreads();
@@ -510,12 +527,12 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     }
     if (t + 1 < T)
       for (int a = 0; a < a_dim; ++a) nz[a] = nz_next[a];
-    if (ENV == 0) {
+    if constexpr (ENV == 0) {
       MountainCar::step(pp, vv, act[0]);
       x0 = pp;
       x1 = vv;
     } else {
-      GridWorld::step(gx, gy, act[0], act[1]);
+      grid_step<ENV>(gx, gy, act[0], act[1], mz...);
       x0 = (double)gx;
       x1 = (double)gy;
     }
@@ -621,20 +638,20 @@ static size_t rollout_mw_bytes(int64_t n, int64_t T, int h1, int a_dim) {
 // [h0][64] f64 slice (dynamic) + sh1, spart, sword (static, 6.5 KB) within 160 KB of LDS
 static constexpr int kRollMwMaxH0 = 306;
 
-template <int ENV, int GOAL = kGoalNone>
+template <int ENV, int GOAL = kGoalNone, typename... MZ>
 static int rollout_mw_prepare() {
-  MEPOL_HIP((max_dynamic_lds<rollout_mlp_mw_kernel<ENV, false, GOAL>>(
+  MEPOL_HIP((max_dynamic_lds<rollout_mlp_mw_kernel<ENV, false, GOAL, MZ...>>(
       kRollMwMaxH0 * 64 * (int)sizeof(double))));
   return 0;
 }
 
 // Workgroups of the <ENV, GOAL> instance a CU holds at this dynamic LDS size; 0 on any error.
-template <int ENV, int GOAL>
+template <int ENV, int GOAL, typename... MZ>
 static int rollout_mw_per_cu(size_t lds) {
   int per_cu = 0;
-  if (rollout_mw_prepare<ENV, GOAL>()) return 0;
+  if (rollout_mw_prepare<ENV, GOAL, MZ...>()) return 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &per_cu, rollout_mlp_mw_kernel<ENV, false, GOAL>, 64 * kRollMwWaves, lds) !=
+          &per_cu, rollout_mlp_mw_kernel<ENV, false, GOAL, MZ...>, 64 * kRollMwWaves, lds) !=
       hipSuccess) {
     (void)hipGetLastError();
     return 0;
@@ -652,7 +669,8 @@ static int rollout_mw_per_cu(size_t lds) {
 // faulted inside libhsa-runtime64 after the profiler had shut its queue interception down,
 // profiles/r5/rollout_exit_crash.txt.)
 // The occupancy asked is that of the instance that will run, env x goal kind: each has its own
-// register count.
+// register count.  The maze (env 2) takes no LDS (its description is a kernel argument), so the
+// LDS sizes here and the KL budget of the one-workgroup form are those of the other envs.
 static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim,
                           int goal = kGoalNone) {
   const int np = (h1 + 63) / 64;
@@ -664,7 +682,11 @@ static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim,
     return 0;
   const size_t lds = (size_t)h0 * 64 * sizeof(double);
   int per_cu;
-  if (goal == kGoalBall)  // (env 1 only)
+  if (env_id == 2)
+    per_cu = goal == kGoalBall        ? rollout_mw_per_cu<2, kGoalBall, MazeArgs>(lds)
+             : goal == kGoalThreshold ? rollout_mw_per_cu<2, kGoalThreshold, MazeArgs>(lds)
+                                      : rollout_mw_per_cu<2, kGoalNone, MazeArgs>(lds);
+  else if (goal == kGoalBall)  // (env 1)
     per_cu = rollout_mw_per_cu<1, kGoalBall>(lds);
   else if (goal == kGoalThreshold)
     per_cu = env_id == 0 ? rollout_mw_per_cu<0, kGoalThreshold>(lds)
@@ -701,7 +723,7 @@ extern "C" int mepol_rollout_mlp_workspace_size(int64_t n, int64_t T, int h0, in
   return 0;
 }
 
-template <int ENV, int GOAL = kGoalNone>
+template <int ENV, int GOAL = kGoalNone, typename... MZ>
 static hipError_t rollout_mw_launch(const double* W1, const double* b1, int h0,
                                     const double* W2t, const double* b2, int h1, const double* Wm,
                                     const double* bm, const double* log_std, int a_dim,
@@ -709,13 +731,14 @@ static hipError_t rollout_mw_launch(const double* W1, const double* b1, int h0,
                                     const double* noise, int64_t n, int64_t T, float* states_rec,
                                     float* actions_rec, double* visited, double* final_state,
                                     int np, int nw, unsigned long long* mail, int* err,
-                                    int* ticket, const GoalArgs& goal, hipStream_t st) {
+                                    int* ticket, const GoalArgs& goal, hipStream_t st,
+                                    const MZ&... mz) {
   long long* probe = nullptr;
-  hipLaunchKernelGGL((rollout_mlp_mw_kernel<ENV, false, GOAL>), dim3((unsigned)(n * np)),
+  hipLaunchKernelGGL((rollout_mlp_mw_kernel<ENV, false, GOAL, MZ...>), dim3((unsigned)(n * np)),
                      dim3(64 * kRollMwWaves), (unsigned)((size_t)h0 * 64 * sizeof(double)), st,
                      W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T,
                      states_rec, actions_rec, visited, final_state, np, nw, mail, err, ticket,
-                     probe, goal);
+                     probe, goal, mz...);
   return hipGetLastError();
 }
 
@@ -737,6 +760,7 @@ extern "C" int mepol_rollout_goal_plan_info(int64_t n, int h0, int h1, int a_dim
 // mepol_rollout_mlp (goal == nullptr), mepol_rollout_goal (kind kGoalBall, env 1) and
 // mepol_rollout_goal_threshold (kind kGoalThreshold) behind their argument checks: the same
 // choice of form, workspace layout and launches, the kernels' GOAL instances for the last two.
+// env_id 2 (mepol_rollout_maze, any kind): the ENV = 2 instances with *mz, already validated.
 static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h0,
                            const double* W2t, const double* b2, int h1, const double* Wm,
                            const double* bm, const double* log_std, int a_dim,
@@ -744,7 +768,7 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
                            int64_t n, int64_t T, float* states_rec, float* actions_rec,
                            double* visited, double* final_state, const GoalArgs* goal,
                            void* workspace, size_t workspace_bytes, void* stream,
-                           int kind = kGoalBall) {
+                           int kind = kGoalBall, const MazeArgs* mz = nullptr) {
   const GoalArgs ga = goal ? *goal : GoalArgs{};
   if (!goal) kind = kGoalNone;
   const int threads = ((h0 > h1 ? h0 : h1) + 63) / 64 * 64;
@@ -765,12 +789,20 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
   rollout_mw_launch<E, G>(W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, \
                           n, T, states_rec, actions_rec, visited, final_state, np, nw, mail, err, \
                           ticket, ga, st)
+#define MEPOL_ROLL_MW_MAZE(G)                                                                     \
+  rollout_mw_launch<2, G, MazeArgs>(W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64,      \
+                                    init32, noise, n, T, states_rec, actions_rec, visited,        \
+                                    final_state, np, nw, mail, err, ticket, ga, st, *mz)
       const hipError_t e =
-          kind == kGoalBall ? MEPOL_ROLL_MW(1, kGoalBall)
+          env_id == 2 ? (kind == kGoalBall        ? MEPOL_ROLL_MW_MAZE(kGoalBall)
+                         : kind == kGoalThreshold ? MEPOL_ROLL_MW_MAZE(kGoalThreshold)
+                                                  : MEPOL_ROLL_MW_MAZE(kGoalNone))
+          : kind == kGoalBall ? MEPOL_ROLL_MW(1, kGoalBall)
           : kind == kGoalThreshold
               ? (env_id == 0 ? MEPOL_ROLL_MW(0, kGoalThreshold) : MEPOL_ROLL_MW(1, kGoalThreshold))
               : (env_id == 0 ? MEPOL_ROLL_MW(0, kGoalNone) : MEPOL_ROLL_MW(1, kGoalNone));
 #undef MEPOL_ROLL_MW
+#undef MEPOL_ROLL_MW_MAZE
       if (e == hipSuccess) return 0;
       (void)hipGetLastError();  // launch refused: the one-workgroup form
     }
@@ -789,7 +821,20 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
                        b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T, states_rec,   \
                        actions_rec, visited, final_state, KL, ga);                                \
   } while (0)
-  if (kind == kGoalBall)
+#define MEPOL_ROLL_MAZE(G)                                                                        \
+  do {                                                                                            \
+    MEPOL_HIP((max_dynamic_lds<rollout_mlp_kernel<2, 8, G, MazeArgs>>(150 * 1024)));              \
+    hipLaunchKernelGGL((rollout_mlp_kernel<2, 8, G, MazeArgs>), g, dim3(threads), lds, st, W1, b1, \
+                       h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T,      \
+                       states_rec, actions_rec, visited, final_state, KL, ga, *mz);               \
+  } while (0)
+  if (env_id == 2 && kind == kGoalBall)
+    MEPOL_ROLL_MAZE(kGoalBall);
+  else if (env_id == 2 && kind == kGoalThreshold)
+    MEPOL_ROLL_MAZE(kGoalThreshold);
+  else if (env_id == 2)
+    MEPOL_ROLL_MAZE(kGoalNone);
+  else if (kind == kGoalBall)
     MEPOL_ROLL(1, 8, kGoalBall);
   else if (kind == kGoalThreshold && env_id == 0)
     MEPOL_ROLL(0, 8, kGoalThreshold);
@@ -800,6 +845,7 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
   else
     MEPOL_ROLL(1, 8, kGoalNone);
 #undef MEPOL_ROLL
+#undef MEPOL_ROLL_MAZE
   MEPOL_CHECK_LAUNCH();
   return 0;
 }
@@ -930,4 +976,111 @@ extern "C" int mepol_rollout_goal_threshold(
   return rollout_mlp_run(env_id, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32,
                          noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
                          workspace_bytes, stream, kGoalThreshold);
+}
+
+// ---- box mazes (env 2) -------------------------------------------------------------------------
+// The env_id 1 entry points above folded by goal kind (include/mepol_amd.h): the ENV = 2 instances
+// behind the same argument checks plus maze_args_ok.
+extern "C" int mepol_step_maze(const mepol_maze* maze, float* state, const double* action,
+                               int64_t n, void* stream) {
+  if (!maze_args_ok(maze, "mepol_step_maze")) return kErrBadArg;
+  if (n <= 0) return 0;
+  if (!state || !action) {
+    set_error("mepol_step_maze: null state or action");
+    return kErrBadArg;
+  }
+  hipLaunchKernelGGL(step_maze_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, state, action, n, *maze);
+  MEPOL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mepol_rollout_step_maze(const mepol_maze* maze, float* env_f32, const double* mean,
+                                       const double* noise, const double* log_std, int64_t n,
+                                       int a_dim, int64_t t, int64_t T, float* states_rec,
+                                       float* actions_rec, double* policy_in, void* stream) {
+  if (!maze_args_ok(maze, "mepol_rollout_step_maze")) return kErrBadArg;
+  if (a_dim != 2 || t < 0 || t >= T || !env_f32 || !mean || !noise || !log_std || !states_rec ||
+      !actions_rec || !policy_in) {
+    set_error("mepol_rollout_step_maze: bad arguments (a_dim %d must be 2, t %lld in [0, T), no "
+              "null pointers)", a_dim, (long long)t);
+    return kErrBadArg;
+  }
+  if (n <= 0) return 0;
+  double* env_f64 = nullptr;
+  hipLaunchKernelGGL((rollout_step_kernel<2, MazeArgs>), dim3((unsigned)((n + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream, env_f64, env_f32, mean, noise, log_std, n,
+                     a_dim, t, T, states_rec, actions_rec, policy_in, *maze);
+  MEPOL_CHECK_LAUNCH();
+  return 0;
+}
+
+static bool maze_kind_ok(int goal_kind) {
+  return goal_kind == kGoalNone || goal_kind == kGoalBall || goal_kind == kGoalThreshold;
+}
+
+static bool maze_shape_ok(int goal_kind, int h0, int h1, int a_dim) {
+  return maze_kind_ok(goal_kind) && h0 > 0 && h1 > 0 && h0 <= kRollMaxH && h1 <= kRollMaxH &&
+         a_dim == 2;
+}
+
+extern "C" int mepol_rollout_maze_plan_info(int goal_kind, int64_t n, int h0, int h1, int a_dim,
+                                            int* workgroups_per_traj, int* k_chunks) {
+  if (n <= 0 || !maze_shape_ok(goal_kind, h0, h1, a_dim) || !workgroups_per_traj || !k_chunks) {
+    set_error("mepol_rollout_maze_plan_info: bad arguments (goal kind 0 .. 2, a_dim = 2, hidden "
+              "<= %d)", kRollMaxH);
+    return kErrBadArg;
+  }
+  const int mw = rollout_use_mw(2, n, h0, h1, a_dim, goal_kind);
+  *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
+  *k_chunks = kRollChunks;  // both forms
+  return 0;
+}
+
+extern "C" int mepol_rollout_maze_workspace_size(int goal_kind, int64_t n, int64_t T, int h0,
+                                                 int h1, int a_dim, size_t* bytes) {
+  if (n < 0 || T < 0 || !maze_shape_ok(goal_kind, h0, h1, a_dim) || !bytes) {
+    set_error("mepol_rollout_maze_workspace_size: bad arguments (goal kind 0 .. 2, a_dim = 2, "
+              "hidden <= %d)", kRollMaxH);
+    return kErrBadArg;
+  }
+  *bytes = (n > 0 && rollout_use_mw(2, n, h0, h1, a_dim, goal_kind))
+               ? rollout_mw_bytes(n, T, h1, a_dim)
+               : 256;
+  return 0;
+}
+
+extern "C" int mepol_rollout_maze(const mepol_maze* maze, int goal_kind, const double* W1,
+                                  const double* b1, int h0, const double* W2t, const double* b2,
+                                  int h1, const double* Wm, const double* bm,
+                                  const double* log_std, int a_dim, const float* init32,
+                                  const double* noise, int64_t n, int64_t T, float goal_x,
+                                  float goal_y, int coord, double goal_value, float* states_rec,
+                                  float* actions_rec, double* visited, double* final_state,
+                                  float* rewards_rec, int32_t* len_out, int32_t* done_out,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (!maze_args_ok(maze, "mepol_rollout_maze")) return kErrBadArg;
+  const bool goal_ok =
+      goal_kind == kGoalNone ||
+      (rewards_rec && len_out && done_out && T <= INT32_MAX &&
+       (goal_kind == kGoalBall ? goal_x == goal_x && goal_y == goal_y && goal_value >= 0.0
+                               : (coord == 0 || coord == 1) && goal_value == goal_value));
+  if (!maze_shape_ok(goal_kind, h0, h1, a_dim) || !goal_ok || !init32 || !W1 || !b1 || !W2t ||
+      !b2 || !Wm || !bm || !log_std || !noise || !states_rec || !actions_rec ||
+      (workspace && workspace_bytes < sizeof(int))) {
+    set_error("mepol_rollout_maze: bad arguments (goal kind 0 .. 2, hidden <= %d, a_dim = 2; "
+              "ball: radius >= 0; threshold: coord 0 or 1, threshold not NaN; no null pointers)",
+              kRollMaxH);
+    return kErrBadArg;
+  }
+  if (n <= 0 || T <= 0) return 0;
+  GoalArgs goal{};
+  if (goal_kind == kGoalBall)
+    goal = GoalArgs{{goal_x}, goal_y, {goal_value}, rewards_rec, len_out, done_out};
+  else if (goal_kind == kGoalThreshold)
+    goal = threshold_goal(coord, goal_value, rewards_rec, len_out, done_out);
+  return rollout_mlp_run(2, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, nullptr, init32,
+                         noise, n, T, states_rec, actions_rec, visited, final_state,
+                         goal_kind == kGoalNone ? nullptr : &goal, workspace, workspace_bytes,
+                         stream, goal_kind, maze);
 }

@@ -3,9 +3,11 @@
 // (wrappers.py:40-52).  The kernels' GOAL template argument names the kind of goal, so that each
 // instance holds one hit test and no run-time choice between them:
 //   kGoalNone       no goal mode (GoalArgs is never read);
-//   kGoalBall       GridWorld only: the f32 state within `radius` of the f32 goal (goal_hit);
-//   kGoalThreshold  either env: state[coord] >= threshold on the env's own state, MountainCar's
-//                   f64 (p, v) or GridWorld's f32 (sx, sy) widened exactly (goal_hit_threshold).
+//   kGoalBall       GridWorld and the maze (the f32-state envs): the f32 state within `radius` of
+//                   the f32 goal (goal_hit);
+//   kGoalThreshold  any env: state[coord] >= threshold on the env's own state, MountainCar's
+//                   f64 (p, v) or GridWorld's / the maze's f32 (sx, sy) widened exactly
+//                   (goal_hit_threshold).
 // After each env step the state is tested; a hit at step t gives rewards[i, t] = 1,
 // len[i] = t + 1, done[i] = 1, s_{t+1} is recorded and the trajectory's workgroup(s) leave.  Every
 // output row past the end is written as zeros, so the caller's buffers need no clearing.
@@ -59,12 +61,13 @@ __device__ __forceinline__ bool goal_hit_threshold(double s0, double s1, const G
   return (g.coord ? s1 : s0) >= g.threshold;
 }
 
-// The hit test of a GOAL instance on ENV's state: (p, v) is MountainCar's, (gx, gy) GridWorld's.
+// The hit test of a GOAL instance on ENV's state: (p, v) is MountainCar's, (gx, gy) GridWorld's
+// and the maze's.
 template <int GOAL, int ENV>
 __device__ __forceinline__ bool goal_test(double p, double v, float gx, float gy,
                                           const GoalArgs& g) {
   static_assert(GOAL == kGoalBall || GOAL == kGoalThreshold, "a goal kind");
-  static_assert(GOAL != kGoalBall || ENV == 1, "the ball goal is GridWorld's");
+  static_assert(GOAL != kGoalBall || ENV != 0, "the ball goal needs an f32-state env");
   if constexpr (GOAL == kGoalBall)
     return goal_hit(gx, gy, g);
   else if constexpr (ENV == 0)

@@ -1,6 +1,7 @@
 // Whole rollout in one launch for ReLU policies with 3 to 6 hidden layers (mepol_rollout_deep):
 // all T steps of collect_particles (mepol.py:81-90) for nf = 2 -> [h_1 .. h_L] -> a_dim in f64
-// on MountainCar / GridWorld.  One workgroup per trajectory, as rollout_mlp_kernel (envs.hip):
+// on MountainCar / GridWorld / a box maze (ENV 2, mepol_rollout_deep_maze).  One workgroup per
+// trajectory, as rollout_mlp_kernel (envs.hip):
 // thread j owns column j of every layer.  Layer 1 (nf = 2) runs from registers; the hidden
 // activations ping-pong between two LDS vectors; the transposed weights W_l^T ([h_{l-1}][h_l],
 // k-major) of layers 2 .. L are read coalesced from L2 every step (one 8-byte word per thread
@@ -90,7 +91,8 @@ __device__ __forceinline__ double deep_column(const double* __restrict__ sw,
   return acc;
 }
 
-template <int ENV, int GOAL = kGoalNone>
+// MZ: MazeArgs for ENV 2 (the box maze), else empty (grid_step, env_step.hpp).
+template <int ENV, int GOAL = kGoalNone, typename... MZ>
 __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, const double* __restrict__ Wt,
     const double* __restrict__ bt, const double* __restrict__ Wm, const double* __restrict__ bm,
@@ -98,8 +100,8 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     const float* __restrict__ init32, const double* __restrict__ noise, int64_t n, int64_t T,
     float* __restrict__ states_rec, float* __restrict__ actions_rec,
     double* __restrict__ visited, double* __restrict__ final_state, DeepShape sh,
-    GoalArgs goal) {
-  static_assert(GOAL != kGoalBall || ENV == 1, "the ball goal is GridWorld's");
+    GoalArgs goal, MZ... mz) {
+  static_assert(GOAL != kGoalBall || ENV != 0, "the ball goal needs an f32-state env");
   extern __shared__ double sW[];  // resident rows of W_2^T .. W_L^T, layer after layer
   __shared__ double sx[2];
   __shared__ int sgoal;  // GOAL: the step just taken reached the goal (thread 0 writes it)
@@ -213,12 +215,12 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
       }
       if (t + 1 < T)
         for (int a = 0; a < a_dim; ++a) nz[a] = nz_next[a];
-      if (ENV == 0) {
+      if constexpr (ENV == 0) {
         MountainCar::step(p, v, act[0]);
         sx[0] = p;
         sx[1] = v;
       } else {
-        GridWorld::step(gx, gy, act[0], act[1]);
+        grid_step<ENV>(gx, gy, act[0], act[1], mz...);
         sx[0] = (double)gx;
         sx[1] = (double)gy;
       }
@@ -310,13 +312,15 @@ static DeepPlan deep_plan(int n_hidden, const int* widths) {
 
 // mepol_rollout_deep (goal == nullptr), mepol_rollout_deep_goal (kind kGoalBall, env 1) and
 // mepol_rollout_deep_goal_threshold (kind kGoalThreshold) behind their argument checks: the same
-// plan, workspace header and launch, the kernel's GOAL instances for the last two.
+// plan, workspace header and launch, the kernel's GOAL instances for the last two.  env_id 2
+// (mepol_rollout_deep_maze, any kind): the ENV = 2 instances with *mz, already validated.
 static int deep_run(int env_id, int n_hidden, const int* widths, const double* W1,
                     const double* b1, const double* Wt, const double* bt, const double* Wm,
                     const double* bm, const double* log_std, int a_dim, const double* init64,
                     const float* init32, const double* noise, int64_t n, int64_t T,
                     float* states_rec, float* actions_rec, double* visited, double* final_state,
-                    const GoalArgs* goal, void* workspace, void* stream, int kind = kGoalBall) {
+                    const GoalArgs* goal, void* workspace, void* stream, int kind = kGoalBall,
+                    const MazeArgs* mz = nullptr) {
   const DeepPlan p = deep_plan(n_hidden, widths);
   const GoalArgs ga = goal ? *goal : GoalArgs{};
   if (!goal) kind = kGoalNone;
@@ -330,7 +334,20 @@ static int deep_run(int env_id, int n_hidden, const int* widths, const double* W
                        log_std, a_dim, init64, init32, noise, n, T, states_rec, actions_rec,      \
                        visited, final_state, p.sh, ga);                                           \
   } while (0)
-  if (kind == kGoalBall)
+#define MEPOL_DEEP_MAZE(G)                                                                        \
+  do {                                                                                            \
+    MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<2, G, MazeArgs>>(kDeepLdsBytes)));             \
+    hipLaunchKernelGGL((rollout_deep_kernel<2, G, MazeArgs>), g, b, p.lds, st, W1, b1, Wt, bt, Wm, \
+                       bm, log_std, a_dim, init64, init32, noise, n, T, states_rec, actions_rec,  \
+                       visited, final_state, p.sh, ga, *mz);                                      \
+  } while (0)
+  if (env_id == 2 && kind == kGoalBall)
+    MEPOL_DEEP_MAZE(kGoalBall);
+  else if (env_id == 2 && kind == kGoalThreshold)
+    MEPOL_DEEP_MAZE(kGoalThreshold);
+  else if (env_id == 2)
+    MEPOL_DEEP_MAZE(kGoalNone);
+  else if (kind == kGoalBall)
     MEPOL_DEEP(1, kGoalBall);
   else if (kind == kGoalThreshold && env_id == 0)
     MEPOL_DEEP(0, kGoalThreshold);
@@ -341,21 +358,22 @@ static int deep_run(int env_id, int n_hidden, const int* widths, const double* W
   else
     MEPOL_DEEP(1, kGoalNone);
 #undef MEPOL_DEEP
+#undef MEPOL_DEEP_MAZE
   MEPOL_CHECK_LAUNCH();
   return 0;
 }
 
 // Workgroups of the <ENV, GOAL> instance the device holds at once for this shape: the kernel's
 // occupancy at the block size and dynamic LDS the launcher chooses, times the CU count.
-template <int ENV, int GOAL>
+template <int ENV, int GOAL, typename... MZ>
 static int deep_resident(int n_hidden, const int* widths, int* resident_workgroups) {
   const DeepPlan p = deep_plan(n_hidden, widths);
   int dev = 0, cus = 0, per_cu = 0;
   MEPOL_HIP(hipGetDevice(&dev));
   MEPOL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<ENV, GOAL>>(kDeepLdsBytes)));
+  MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<ENV, GOAL, MZ...>>(kDeepLdsBytes)));
   MEPOL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, rollout_deep_kernel<ENV, GOAL>, (int)p.threads, p.lds));
+      &per_cu, rollout_deep_kernel<ENV, GOAL, MZ...>, (int)p.threads, p.lds));
   *resident_workgroups = per_cu * cus;
   return 0;
 }
@@ -502,4 +520,72 @@ extern "C" int mepol_rollout_deep_goal_threshold_plan_info(int env_id, int n_hid
   }
   return env_id == 0 ? deep_resident<0, kGoalThreshold>(n_hidden, widths, resident_workgroups)
                      : deep_resident<1, kGoalThreshold>(n_hidden, widths, resident_workgroups);
+}
+
+// ---- box mazes (env 2) -------------------------------------------------------------------------
+// mepol_rollout_deep, mepol_rollout_deep_goal and mepol_rollout_deep_goal_threshold folded by goal
+// kind (include/mepol_amd.h): the ENV = 2 instances behind the same checks plus maze_args_ok.
+static int deep_maze_bad_args(const char* who) {
+  set_error("%s: bad arguments (goal kind 0 .. 2, %d <= n_hidden <= %d, 1 <= width <= %d, "
+            "a_dim = 2; ball: radius >= 0; threshold: coord 0 or 1, threshold not NaN; no null "
+            "pointers)",
+            who, kDeepMinL, kDeepMaxL, kDeepMaxH);
+  return kErrBadArg;
+}
+
+static bool deep_maze_shape_ok(int goal_kind, int n_hidden, const int* widths, int a_dim) {
+  return (goal_kind == kGoalNone || goal_kind == kGoalBall || goal_kind == kGoalThreshold) &&
+         a_dim == 2 && deep_shape_ok(1, n_hidden, widths, a_dim);
+}
+
+extern "C" int mepol_rollout_deep_maze_workspace_size(int64_t n, int64_t T, int n_hidden,
+                                                      const int* widths, int a_dim,
+                                                      size_t* bytes) {
+  if (n < 0 || T < 0 || !bytes || !deep_maze_shape_ok(kGoalNone, n_hidden, widths, a_dim))
+    return deep_maze_bad_args("mepol_rollout_deep_maze_workspace_size");
+  *bytes = kDeepWorkspaceBytes;
+  return 0;
+}
+
+extern "C" int mepol_rollout_deep_maze_plan_info(int goal_kind, int n_hidden, const int* widths,
+                                                 int a_dim, int* resident_workgroups) {
+  if (!resident_workgroups || !deep_maze_shape_ok(goal_kind, n_hidden, widths, a_dim))
+    return deep_maze_bad_args("mepol_rollout_deep_maze_plan_info");
+  return goal_kind == kGoalBall
+             ? deep_resident<2, kGoalBall, MazeArgs>(n_hidden, widths, resident_workgroups)
+         : goal_kind == kGoalThreshold
+             ? deep_resident<2, kGoalThreshold, MazeArgs>(n_hidden, widths, resident_workgroups)
+             : deep_resident<2, kGoalNone, MazeArgs>(n_hidden, widths, resident_workgroups);
+}
+
+extern "C" int mepol_rollout_deep_maze(
+    const mepol_maze* maze, int goal_kind, int n_hidden, const int* widths, const double* W1,
+    const double* b1, const double* Wt, const double* bt, const double* Wm, const double* bm,
+    const double* log_std, int a_dim, const float* init32, const double* noise, int64_t n,
+    int64_t T, float goal_x, float goal_y, int coord, double goal_value, float* states_rec,
+    float* actions_rec, double* visited, double* final_state, float* rewards_rec,
+    int32_t* len_out, int32_t* done_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!maze_args_ok(maze, "mepol_rollout_deep_maze")) return kErrBadArg;
+  const bool goal_ok =
+      goal_kind == kGoalNone ||
+      (rewards_rec && len_out && done_out && T <= INT32_MAX &&
+       (goal_kind == kGoalBall ? goal_x == goal_x && goal_y == goal_y && goal_value >= 0.0
+                               : (coord == 0 || coord == 1) && goal_value == goal_value));
+  if (!deep_maze_shape_ok(goal_kind, n_hidden, widths, a_dim) || !goal_ok || !init32 || !W1 ||
+      !b1 || !Wt || !bt || !Wm || !bm || !log_std || !noise || !states_rec || !actions_rec)
+    return deep_maze_bad_args("mepol_rollout_deep_maze");
+  if (workspace && workspace_bytes < kDeepWorkspaceBytes) {
+    set_error("mepol_rollout_deep_maze: workspace of %zu bytes, %zu needed", workspace_bytes,
+              kDeepWorkspaceBytes);
+    return kErrWorkspace;
+  }
+  if (n <= 0 || T <= 0) return 0;
+  GoalArgs goal{};
+  if (goal_kind == kGoalBall)
+    goal = GoalArgs{{goal_x}, goal_y, {goal_value}, rewards_rec, len_out, done_out};
+  else if (goal_kind == kGoalThreshold)
+    goal = threshold_goal(coord, goal_value, rewards_rec, len_out, done_out);
+  return deep_run(2, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, nullptr, init32,
+                  noise, n, T, states_rec, actions_rec, visited, final_state,
+                  goal_kind == kGoalNone ? nullptr : &goal, workspace, stream, goal_kind, maze);
 }

@@ -30,6 +30,11 @@ of the reached state alone, defined for whole batches), and so is any such rewar
 they sample on the un-terminated one-launch rollouts, cut at each trajectory's first done
 (algorithms/trpo.py).  A plain function reward keeps the reference's one-env host loop.
 
+--env FourRoomsGoal (a build extension) is the far corner of the four-rooms maze of
+`mepol --env FourRooms`, CustomRewardEnv(BoxMazeContinuous.four_rooms(), GridGoal((5, 5))), with
+the GridGoal policy, so that command line's checkpoints load.  It samples on the one-launch goal
+rollouts, as every GridGoal, ThresholdGoal or BatchReward over a BoxMazeContinuous does.
+
 MuJoCo goals (AntEscape, AntNavigate, AntJump, HumanoidUp) keep their specs but need mujoco-py,
 which is outside this build's scope.
 """
@@ -49,7 +54,7 @@ def build_parser():
                    help="How many parallel workers to use when collecting samples")
     p.add_argument("--env", type=str, required=True,
                    help="The MDP (build extensions: MountainCarGoal, GridGoalAny, "
-                        "MountainCarLeft)")
+                        "MountainCarLeft, FourRoomsGoal)")
     p.add_argument("--policy_init", type=str, default=None,
                    help="Path to the weights for custom policy initialization.")
     p.add_argument("--num_epochs", type=int, required=True, help="The number of training epochs")
@@ -90,8 +95,8 @@ def checkpoint_widths(state_dict):
 
 
 def exp_specs():
-    from ..envs import (AnyGoal, BoxGoal, CustomRewardEnv, GridGoal, GridWorldContinuous,
-                        MountainCarContinuous, ThresholdGoal)
+    from ..envs import (AnyGoal, BoxGoal, BoxMazeContinuous, CustomRewardEnv, GridGoal,
+                        GridWorldContinuous, MountainCarContinuous, ThresholdGoal)
 
     def grid_reward(make_reward):
         return dict(env_create=lambda: CustomRewardEnv(GridWorldContinuous(), make_reward()),
@@ -113,6 +118,10 @@ def exp_specs():
             "GridGoalAny": grid_reward(lambda: AnyGoal(GridGoal((5, 5)), GridGoal((2, 5)),
                                                        GridGoal((5, 2)))),
             "MountainCarLeft": mountain_car_reward(lambda: BoxGoal((-inf, -inf), (-1.1, inf))),
+            "FourRoomsGoal": dict(
+                env_create=lambda: CustomRewardEnv(BoxMazeContinuous.four_rooms(),
+                                                   GridGoal((5, 5))),
+                hidden_sizes=[300, 300], activation=nn.ReLU, log_std_init=-1.5),
             "AntEscape": dict(mujoco), "AntNavigate": dict(mujoco), "AntJump": dict(mujoco),
             "HumanoidUp": dict(mujoco)}
 

@@ -9,6 +9,12 @@ directory layout and log_info.txt.  Runs the hot path on the GPU:
         --heatmap_episodes 100 --heatmap_num_steps 1200 --use_backtracking 1 \
         --zero_mean_start 1 --full_entropy_traj_scale 5 --full_entropy_k 50 --num_workers 1
 
+--env FourRooms (a build extension: the reference has only the GridWorld layout) is
+ErgodicEnv(BoxMazeContinuous.four_rooms()), a +-6 square split into four rooms by a cross of walls
+with one door per arm, with GridWorld's policy spec and a 20 x 20 discretizer over its bounds.  Any
+BoxMazeContinuous (envs/maze.py: bounds, step size, start box and up to 16 wall boxes are data)
+rolls out on the same one-launch kernels as GridWorld.
+
 MuJoCo environments (Ant, AntXY, Humanoid, HumanoidXYZ, HandReach) keep their specs but need
 mujoco-py, which is outside this build's scope.  Heatmaps are computed on the GPU
 (algorithms/mepol.py::get_heatmap) with the specs' discretizers.
@@ -27,7 +33,8 @@ def build_parser():
     p = argparse.ArgumentParser(description="MEPOL")
     p.add_argument("--num_workers", type=int, default=1,
                    help="How many parallel workers to use when collecting env trajectories and compute k-nn")
-    p.add_argument("--env", type=str, required=True, help="The MDP")
+    p.add_argument("--env", type=str, required=True,
+                   help="The MDP (build extension: FourRooms)")
     p.add_argument("--zero_mean_start", type=int, default=1, choices=[0, 1],
                    help="Whether to make the policy start from a zero mean output")
     p.add_argument("--k", type=int, required=True, help="The number of neighbors")
@@ -72,7 +79,7 @@ def build_parser():
 
 
 def exp_specs():
-    from ..envs import ErgodicEnv, GridWorldContinuous, MountainCarContinuous
+    from ..envs import BoxMazeContinuous, ErgodicEnv, GridWorldContinuous, MountainCarContinuous
     from ..envs.discretizer import Discretizer
 
     xy = dict(discretizer_create=lambda env: Discretizer([[-12.0, 12.0], [-12.0, 12.0]], [40, 40],
@@ -91,6 +98,11 @@ def exp_specs():
         "GridWorld": dict(env_create=lambda: ErgodicEnv(GridWorldContinuous()),
                           discretizer_create=lambda env: Discretizer(
                               [[-env.dim, env.dim], [-env.dim, env.dim]], [20, 20]),
+                          hidden_sizes=[300, 300], activation=nn.ReLU, log_std_init=-1.5, eps=0,
+                          heatmap_interp=None, heatmap_cmap="Blues", heatmap_labels=("X", "-Y")),
+        "FourRooms": dict(env_create=lambda: ErgodicEnv(BoxMazeContinuous.four_rooms()),
+                          discretizer_create=lambda env: Discretizer(
+                              [list(env.bounds[:2]), list(env.bounds[2:])], [20, 20]),
                           hidden_sizes=[300, 300], activation=nn.ReLU, log_std_init=-1.5, eps=0,
                           heatmap_interp=None, heatmap_cmap="Blues", heatmap_labels=("X", "-Y")),
         "Ant": dict(mujoco, **xy, state_filter=list(range(7))),

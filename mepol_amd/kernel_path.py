@@ -84,16 +84,18 @@ def hidden_backward(dz, x, Ws, hs, dW_out=None, db_out=None, dz_out=None, ws_wgr
     return dW, db
 
 
-MOUNTAINCAR, GRIDWORLD = 0, 1  # the kernels' env_id
-ENV_ACTIONS = (1, 2)           # action count of each
+MOUNTAINCAR, GRIDWORLD, MAZE = 0, 1, 2  # the kernels' env_id
+ENV_ACTIONS = (1, 2, 2)                 # action count of each
 
 
 def kernel_env(base):
     """The kernels' env_id for `base`, MOUNTAINCAR (0) or GRIDWORLD (1), when it is exactly a
     MountainCarContinuous or a GridWorldContinuous (no subclass) with the constants the HIP env
-    steps are compiled with (csrc/env_step.hpp), else None: every route that steps an env inside
-    a kernel asks this first."""
+    steps are compiled with (csrc/env_step.hpp), MAZE (2) when it is exactly a BoxMazeContinuous
+    (no subclass: its layout is the kernels' argument, see maze_of), else None: every route that
+    steps an env inside a kernel asks this first."""
     from .envs.gridworld import GridWorldContinuous
+    from .envs.maze import BoxMazeContinuous
     from .envs.mountain_car import MountainCarContinuous
 
     if type(base) is GridWorldContinuous:
@@ -104,7 +106,14 @@ def kernel_env(base):
         # and so are MountainCar's
         if tuple(getattr(base, k) for k in MOUNTAINCAR_FIELDS) == MOUNTAINCAR_DEFAULTS:
             return MOUNTAINCAR
+    elif type(base) is BoxMazeContinuous:
+        return MAZE
     return None
+
+
+def maze_of(base, env_id):
+    """The `maze=` argument of the ops rollout wrappers: `base` itself for MAZE, else None."""
+    return base if env_id == MAZE else None
 
 
 def goal_sampler(env, policy):
@@ -112,8 +121,9 @@ def goal_sampler(env, policy):
     one-launch goal rollout, else None: an f64 policy on the GPU that
     algorithms.mepol._rollout_layers accepts (a 2 -> [h_1 .. h_L] -> a ReLU MLP, widths <= 512),
     and a CustomRewardEnv directly over
-      GridWorldContinuous (the default one, two actions) whose reward is a GridGoal (its f32 goal
-                          and radius are the kernel's arguments) or a ThresholdGoal, or
+      GridWorldContinuous (the default one, two actions) or a BoxMazeContinuous (any layout)
+                          whose reward is a GridGoal (its f32 goal and radius are the kernel's
+                          arguments) or a ThresholdGoal, or
       MountainCarContinuous (exactly that type with the kernel's constants, one action) whose
                           reward is a ThresholdGoal (its index, 0 or 1, and threshold are the
                           kernel's arguments).

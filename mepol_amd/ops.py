@@ -816,21 +816,71 @@ def step_gridworld(state, action):
     return state
 
 
+MAZE = 2  # the kernels' env_id of a box maze (envs/maze.py); 0 MountainCar, 1 GridWorld
+
+
+def maze_struct(maze):
+    """The C ABI's mepol_maze of a BoxMazeContinuous (or any object with its `bounds`,
+    `max_delta` and `walls`).  The library validates it again before every launch."""
+    walls = list(maze.walls)
+    if len(walls) > _lib.MAZE_MAX_WALLS:
+        raise ValueError(f"a maze of {len(walls)} walls: the kernels take at most "
+                         f"{_lib.MAZE_MAX_WALLS}")
+    m = _lib.Maze()
+    m.xlo, m.xhi, m.ylo, m.yhi = (float(v) for v in maze.bounds)
+    m.max_delta = float(maze.max_delta)
+    m.n_walls = len(walls)
+    for w, box in enumerate(walls):
+        for k in range(4):
+            m.walls[w][k] = float(box[k])
+    return m
+
+
+def _maze_arg(who, env_id, maze):
+    """The maze entry points' first argument when env_id is MAZE, else None.  `maze=` belongs to
+    env_id 2 and only there: anything else raises."""
+    if env_id == MAZE:
+        if maze is None:
+            raise ValueError(f"{who}: env_id 2 (box maze) needs maze=")
+        return ctypes.byref(maze if isinstance(maze, _lib.Maze) else maze_struct(maze))
+    if maze is not None:
+        raise ValueError(f"{who}: maze= goes with env_id 2 only (got env_id {env_id})")
+    return None
+
+
+def step_maze(state, action, maze):
+    """In-place batched box-maze step: state f32 [n,2], action f64 [n,2]."""
+    _require_device(state, action)
+    call("mepol_step_maze", _maze_arg("step_maze", MAZE, maze), ptr(state),
+         ptr(action.contiguous()), state.shape[0], _stream())
+    return state
+
+
 def rollout_step(env_id, env_f64, env_f32, mean, noise, log_std, t, T, states_rec, actions_rec,
-                 policy_in):
+                 policy_in, maze=None):
     n, a_dim = mean.shape
+    mz = _maze_arg("rollout_step", env_id, maze)
+    if mz is not None:
+        call("mepol_rollout_step_maze", mz, ptr(env_f32), ptr(mean), ptr(noise), ptr(log_std), n,
+             a_dim, t, T, ptr(states_rec), ptr(actions_rec), ptr(policy_in), _stream())
+        return
     call("mepol_rollout_step", env_id, ptr(env_f64), ptr(env_f32), ptr(mean), ptr(noise),
          ptr(log_std), n, a_dim, t, T, ptr(states_rec), ptr(actions_rec), ptr(policy_in),
          _stream())
 
 
 def rollout_mlp(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, states_rec, actions_rec,
-                visited=None):
-    """All T steps of a batched MountainCar (env_id 0, init f64 [n,2]) / GridWorld (1, init f32)
-    rollout with the 2-hidden-layer ReLU policy in one launch; noise [T, n, a] f64."""
+                visited=None, maze=None):
+    """All T steps of a batched MountainCar (env_id 0, init f64 [n,2]) / GridWorld (1, init f32) /
+    box maze (2, init f32, with maze=) rollout with the 2-hidden-layer ReLU policy in one launch;
+    noise [T, n, a] f64."""
     T, n, a_dim = noise.shape
     h0, h1 = W1.shape[0], W2.shape[0]
     W2t = W2.t().contiguous()
+    mz = _maze_arg("rollout_mlp", env_id, maze)
+    if mz is not None:
+        return _rollout_maze(mz, _lib.GOAL_NONE, W1, b1, W2t, b2, Wm, bm, log_std, init, noise,
+                             states_rec, actions_rec, visited=visited)
     init64 = init.contiguous() if env_id == 0 else None
     init32 = init.contiguous() if env_id == 1 else None
     ws = _ws_or_cached(None, init.device, "rollout", "rollout_mlp", n, T, h0, h1, a_dim)
@@ -850,13 +900,67 @@ def rollout_mlp(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, states_rec
         call("mepol_rollout_mlp", *args, None, 0, _stream())
 
 
+def _rollout_maze(mz, kind, W1, b1, W2t, b2, Wm, bm, log_std, init, noise, states_rec, actions_rec,
+                  visited=None, goal=(0.0, 0.0, 0, 0.0), rewards_rec=None, len_out=None,
+                  done_out=None, defer_check=False):
+    """mepol_rollout_maze behind the two-layer wrappers' own checks: goal = (x, y, coord, value).
+    The error word is handled as the wrapper that called does: re-run at once (returns None), or
+    with defer_check (err, rerun)."""
+    T, n, a_dim = noise.shape
+    h0, h1 = W1.shape[0], W2t.shape[1]
+    if init.dtype != torch.float32:
+        raise ValueError("a box maze's init is f32 [n, 2]")
+    # (contiguous copies stay referenced until the launch is queued)
+    W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
+                                                                          log_std, init, noise))
+    ws = _ws_or_cached(None, init.device, "rollout", "rollout_maze", kind, n, T, h0, h1, a_dim)
+    gx, gy, coord, value = goal
+    args = (mz, kind, ptr(W1), ptr(b1), h0, ptr(W2t), ptr(b2), h1, ptr(Wm), ptr(bm), ptr(log_std),
+            a_dim, ptr(init), ptr(noise), n, T, float(gx), float(gy), int(coord), float(value),
+            ptr(states_rec), ptr(actions_rec), ptr(visited), None, ptr(rewards_rec), ptr(len_out),
+            ptr(done_out))
+    keep = (W1, b1, W2t, b2, Wm, bm, log_std, init, noise)
+    call("mepol_rollout_maze", *args, ptr(ws), ws.numel(), _stream())
+
+    def rerun(_keep=keep):
+        import warnings
+
+        warnings.warn("mepol_rollout_maze: workgroups of a trajectory were not co-resident; "
+                      "re-ran the one-workgroup form")
+        call("mepol_rollout_maze", *args, None, 0, _stream())
+
+    err = ws[:4].view(torch.int32)
+    if defer_check:
+        return err, rerun
+    if n > 0 and T > 0 and int(err[0].item()) != 0:
+        rerun()
+    return None
+
+
+def _rollout_deep_maze(mz, kind, widths, W1, b1, Wt, bt, Wm, bm, log_std, init, noise, states_rec,
+                       actions_rec, visited=None, goal=(0.0, 0.0, 0, 0.0), rewards_rec=None,
+                       len_out=None, done_out=None):
+    """mepol_rollout_deep_maze behind the deep wrappers' own checks: goal = (x, y, coord, value)."""
+    T, n, a_dim = noise.shape
+    if init.dtype != torch.float32:
+        raise ValueError("a box maze's init is f32 [n, 2]")
+    ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep_maze", n, T, len(widths),
+                       widths, a_dim)
+    gx, gy, coord, value = goal
+    call("mepol_rollout_deep_maze", mz, kind, len(widths), widths, ptr(W1), ptr(b1), ptr(Wt),
+         ptr(bt), ptr(Wm), ptr(bm), ptr(log_std), a_dim, ptr(init), ptr(noise), n, T, float(gx),
+         float(gy), int(coord), float(value), ptr(states_rec), ptr(actions_rec), ptr(visited), None,
+         ptr(rewards_rec), ptr(len_out), ptr(done_out), ptr(ws), ws.numel(), _stream())
+
+
 def rollout_deep(env_id, layers, Wm, bm, log_std, init, noise, states_rec, actions_rec,
-                 visited=None):
+                 visited=None, maze=None):
     """rollout_mlp for a ReLU policy with 3 to 6 hidden layers, layers = [(W1, b1), ..., (W_L,
     b_L)] (widths <= 512, odd ones included): all T steps in one launch, one workgroup per
     trajectory (csrc/rollout_deep.hip).  W_2 .. W_L are transposed and packed here per call."""
     _require_device(init, noise, states_rec, actions_rec, visited, Wm, bm, log_std,
                     *[t for p in layers for t in p])
+    mz = _maze_arg("rollout_deep", env_id, maze)
     T, n, a_dim = noise.shape
     (W1, b1), rest = layers[0], layers[1:]
     fan_in = [2] + [W.shape[0] for W, _ in layers]
@@ -868,7 +972,7 @@ def rollout_deep(env_id, layers, Wm, bm, log_std, init, noise, states_rec, actio
         raise ValueError("rollout_deep: tensor shapes do not fit the policy / batch")
     f64 = [t for p in layers for t in p] + [Wm, bm, log_std, noise] + (
         [visited] if visited is not None else []) + ([init] if env_id == 0 else [])
-    if (any(t.dtype != torch.float64 for t in f64) or (env_id == 1 and init.dtype != torch.float32)
+    if (any(t.dtype != torch.float64 for t in f64) or (env_id != 0 and init.dtype != torch.float32)
             or states_rec.dtype != torch.float32 or actions_rec.dtype != torch.float32
             or not (states_rec.is_contiguous() and actions_rec.is_contiguous()
                     and (visited is None or visited.is_contiguous()))):
@@ -879,6 +983,9 @@ def rollout_deep(env_id, layers, Wm, bm, log_std, init, noise, states_rec, actio
     # (contiguous copies stay referenced until the launch is queued)
     W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
                                                                      noise))
+    if mz is not None:
+        return _rollout_deep_maze(mz, _lib.GOAL_NONE, widths, W1, b1, Wt, bt, Wm, bm, log_std, init,
+                                  noise, states_rec, actions_rec, visited=visited)
     init64 = init if env_id == 0 else None
     init32 = init if env_id == 1 else None
     ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
@@ -888,9 +995,26 @@ def rollout_deep(env_id, layers, Wm, bm, log_std, init, noise, states_rec, actio
          ptr(states_rec), ptr(actions_rec), ptr(visited), None, ptr(ws), ws.numel(), _stream())
 
 
-def rollout_mlp_plan(n, h0, h1, a_dim):
+def _maze_plan(kind, n, h0, h1, a_dim):
+    wg, kc = ctypes.c_int(), ctypes.c_int()
+    call("mepol_rollout_maze_plan_info", kind, n, h0, h1, a_dim, ctypes.byref(wg),
+         ctypes.byref(kc))
+    return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
+
+
+def _deep_maze_plan(kind, widths, a_dim):
+    wg = ctypes.c_int()
+    arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
+    call("mepol_rollout_deep_maze_plan_info", kind, len(widths), arr, a_dim, ctypes.byref(wg))
+    return {"resident_workgroups": wg.value}
+
+
+def rollout_mlp_plan(n, h0, h1, a_dim, env_id=None):
     """{"workgroups_per_traj", "k_chunks"}: the form mepol_rollout_mlp takes for this shape and
-    the layer-2 summation order it commits to (oracle.rollout_kordered's k_chunks)."""
+    the layer-2 summation order it commits to (oracle.rollout_kordered's k_chunks).  env_id 2: the
+    maze instance's own answer (MountainCar and GridWorld share one)."""
+    if env_id == MAZE:
+        return _maze_plan(_lib.GOAL_NONE, n, h0, h1, a_dim)
     wg, kc = ctypes.c_int(), ctypes.c_int()
     call("mepol_rollout_mlp_plan_info", n, h0, h1, a_dim, ctypes.byref(wg), ctypes.byref(kc))
     return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
@@ -899,22 +1023,29 @@ def rollout_mlp_plan(n, h0, h1, a_dim):
 def rollout_deep_plan(env_id, widths, a_dim):
     """{"resident_workgroups"}: trajectories of rollout_deep itself (the instance without a goal
     on this env) the device holds at once for hidden layers of these widths."""
+    if env_id == MAZE:
+        return _deep_maze_plan(_lib.GOAL_NONE, widths, a_dim)
     wg = ctypes.c_int()
     arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
     call("mepol_rollout_deep_plan_info", env_id, len(widths), arr, a_dim, ctypes.byref(wg))
     return {"resident_workgroups": wg.value}
 
 
-def rollout_goal_plan(n, h0, h1, a_dim=2):
-    """rollout_mlp_plan for rollout_goal: the form the goal-mode kernel's own occupancy gives."""
+def rollout_goal_plan(n, h0, h1, a_dim=2, env_id=1):
+    """rollout_mlp_plan for rollout_goal: the form the goal-mode kernel's own occupancy gives
+    (env_id 2: the maze's ball-goal instance)."""
+    if env_id == MAZE:
+        return _maze_plan(_lib.GOAL_BALL, n, h0, h1, a_dim)
     wg, kc = ctypes.c_int(), ctypes.c_int()
     call("mepol_rollout_goal_plan_info", n, h0, h1, a_dim, ctypes.byref(wg), ctypes.byref(kc))
     return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
 
 
 def rollout_goal(W1, b1, W2, b2, Wm, bm, log_std, init, noise, goal_xy, radius, states_rec,
-                 actions_rec, rewards_rec, len_out, done_out, env_id=1, defer_check=False):
-    """rollout_mlp on GridWorld (env_id 1) with early termination at a goal: a trajectory ends at
+                 actions_rec, rewards_rec, len_out, done_out, env_id=1, defer_check=False,
+                 maze=None):
+    """rollout_mlp on GridWorld (env_id 1) or a box maze (env_id 2 with maze=) with early
+    termination at a goal: a trajectory ends at
     the first step whose f32 state is within `radius` of goal_xy (reward 1, done), or after T
     steps.  Fills states_rec [n,T+1,2], actions_rec [n,T,2], rewards_rec [n,T] (f32, zeros behind
     each episode's end), len_out and done_out [n] int32; the buffers need no clearing.
@@ -939,6 +1070,13 @@ def rollout_goal(W1, b1, W2, b2, Wm, bm, log_std, init, noise, goal_xy, radius, 
                                                    done_out))):
         raise ValueError("rollout_goal: f64 policy / noise, f32 contiguous records, int32 len / done")
     W2t = W2.t().contiguous()
+    mz = _maze_arg("rollout_goal", env_id, maze)
+    if mz is not None:
+        gx, gy = (float(v) for v in goal_xy)
+        return _rollout_maze(mz, _lib.GOAL_BALL, W1, b1, W2t, b2, Wm, bm, log_std, init, noise,
+                             states_rec, actions_rec, goal=(gx, gy, 0, radius),
+                             rewards_rec=rewards_rec, len_out=len_out, done_out=done_out,
+                             defer_check=defer_check)
     # (contiguous copies stay referenced until the launch is queued)
     W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
                                                                           log_std, init, noise))
@@ -965,9 +1103,12 @@ def rollout_goal(W1, b1, W2, b2, Wm, bm, log_std, init, noise, goal_xy, radius, 
     return None
 
 
-def rollout_deep_goal_plan(widths, a_dim=2):
+def rollout_deep_goal_plan(widths, a_dim=2, env_id=1):
     """{"resident_workgroups"}: trajectories of rollout_deep_goal the device holds at once for
-    hidden layers of these widths (the goal-mode kernel's occupancy times the CU count)."""
+    hidden layers of these widths (the goal-mode kernel's occupancy times the CU count; env_id 2:
+    the maze's ball-goal instance)."""
+    if env_id == MAZE:
+        return _deep_maze_plan(_lib.GOAL_BALL, widths, a_dim)
     wg = ctypes.c_int()
     arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
     call("mepol_rollout_deep_goal_plan_info", len(widths), arr, a_dim, ctypes.byref(wg))
@@ -975,7 +1116,7 @@ def rollout_deep_goal_plan(widths, a_dim=2):
 
 
 def rollout_deep_goal(layers, Wm, bm, log_std, init, noise, goal_xy, radius, states_rec,
-                      actions_rec, rewards_rec, len_out, done_out, env_id=1):
+                      actions_rec, rewards_rec, len_out, done_out, env_id=1, maze=None):
     """rollout_goal for a ReLU policy with 3 to 6 hidden layers, layers = [(W1, b1), ..., (W_L,
     b_L)] as rollout_deep takes them: GridWorld (env_id 1) episodes that end at the first step
     whose f32 state is within `radius` of goal_xy (reward 1, done) or after T steps, in one launch
@@ -1010,6 +1151,11 @@ def rollout_deep_goal(layers, Wm, bm, log_std, init, noise, goal_xy, radius, sta
     W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
                                                                      noise))
     gx, gy = (float(v) for v in goal_xy)
+    mz = _maze_arg("rollout_deep_goal", env_id, maze)
+    if mz is not None:
+        return _rollout_deep_maze(mz, _lib.GOAL_BALL, widths, W1, b1, Wt, bt, Wm, bm, log_std, init,
+                                  noise, states_rec, actions_rec, goal=(gx, gy, 0, radius),
+                                  rewards_rec=rewards_rec, len_out=len_out, done_out=done_out)
     ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
                        a_dim)
     call("mepol_rollout_deep_goal", env_id, len(layers), widths, ptr(W1), ptr(b1), ptr(Wt),
@@ -1021,10 +1167,11 @@ def rollout_deep_goal(layers, Wm, bm, log_std, init, noise, goal_xy, radius, sta
 def _threshold_init(who, env_id, init):
     """The init tensor's dtype rule of the threshold-goal rollouts: f64 for MountainCar (env_id
     0), f32 for GridWorld (1); returns (init64, init32) for the C ABI."""
-    if env_id not in (0, 1):
-        raise ValueError(f"{who}: env_id 0 (MountainCar) or 1 (GridWorld)")
+    if env_id not in (0, 1, MAZE):
+        raise ValueError(f"{who}: env_id 0 (MountainCar), 1 (GridWorld) or 2 (box maze)")
     if init.dtype != (torch.float64 if env_id == 0 else torch.float32):
-        raise ValueError(f"{who}: init is f64 for MountainCar (env_id 0), f32 for GridWorld (1)")
+        raise ValueError(f"{who}: init is f64 for MountainCar (env_id 0), f32 for GridWorld (1) "
+                         "and the box maze (2)")
     return (init, None) if env_id == 0 else (None, init)
 
 
@@ -1032,6 +1179,8 @@ def rollout_goal_threshold_plan(env_id, n, h0, h1, a_dim=None):
     """rollout_goal_plan for rollout_goal_threshold on this env: the form the occupancy of the
     instance that runs (env x threshold goal) gives.  a_dim defaults to the env's."""
     a_dim = (1 if env_id == 0 else 2) if a_dim is None else a_dim
+    if env_id == MAZE:
+        return _maze_plan(_lib.GOAL_THRESHOLD, n, h0, h1, a_dim)
     wg, kc = ctypes.c_int(), ctypes.c_int()
     call("mepol_rollout_goal_threshold_plan_info", env_id, n, h0, h1, a_dim, ctypes.byref(wg),
          ctypes.byref(kc))
@@ -1040,7 +1189,7 @@ def rollout_goal_threshold_plan(env_id, n, h0, h1, a_dim=None):
 
 def rollout_goal_threshold(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, coord, threshold,
                            states_rec, actions_rec, rewards_rec, len_out, done_out,
-                           defer_check=False):
+                           defer_check=False, maze=None):
     """rollout_goal with a threshold goal, on MountainCar (env_id 0, init f64 [n,2], one action)
     or GridWorld (1, init f32, two actions): a trajectory ends at the first step whose state has
     state[coord] >= threshold, compared in f64 on the env's own state (reward 1, done), or after T
@@ -1063,10 +1212,16 @@ def rollout_goal_threshold(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise,
         raise ValueError("rollout_goal_threshold: f64 policy / noise, f32 contiguous records, "
                          "int32 len / done")
     W2t = W2.t().contiguous()
+    mz = _maze_arg("rollout_goal_threshold", env_id, maze)
     # (contiguous copies stay referenced until the launch is queued)
     W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
                                                                           log_std, init, noise))
     init64, init32 = _threshold_init("rollout_goal_threshold", env_id, init)
+    if mz is not None:
+        return _rollout_maze(mz, _lib.GOAL_THRESHOLD, W1, b1, W2t, b2, Wm, bm, log_std, init, noise,
+                             states_rec, actions_rec, goal=(0.0, 0.0, coord, threshold),
+                             rewards_rec=rewards_rec, len_out=len_out, done_out=done_out,
+                             defer_check=defer_check)
     ws = _ws_or_cached(None, init.device, "rollout", "rollout_goal_threshold", env_id, n, T, h0,
                        h1, a_dim)
     args = (env_id, ptr(W1), ptr(b1), h0, ptr(W2t), ptr(b2), h1, ptr(Wm), ptr(bm), ptr(log_std),
@@ -1094,6 +1249,8 @@ def rollout_deep_goal_threshold_plan(env_id, widths, a_dim=None):
     """rollout_deep_goal_plan for rollout_deep_goal_threshold on this env (the occupancy of the
     instance that runs times the CU count).  a_dim defaults to the env's."""
     a_dim = (1 if env_id == 0 else 2) if a_dim is None else a_dim
+    if env_id == MAZE:
+        return _deep_maze_plan(_lib.GOAL_THRESHOLD, widths, a_dim)
     wg = ctypes.c_int()
     arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
     call("mepol_rollout_deep_goal_threshold_plan_info", env_id, len(widths), arr, a_dim,
@@ -1102,7 +1259,8 @@ def rollout_deep_goal_threshold_plan(env_id, widths, a_dim=None):
 
 
 def rollout_deep_goal_threshold(env_id, layers, Wm, bm, log_std, init, noise, coord, threshold,
-                                states_rec, actions_rec, rewards_rec, len_out, done_out):
+                                states_rec, actions_rec, rewards_rec, len_out, done_out,
+                                maze=None):
     """rollout_goal_threshold for a ReLU policy with 3 to 6 hidden layers, layers = [(W1, b1), ...,
     (W_L, b_L)] as rollout_deep takes them: one launch with one workgroup per trajectory
     (csrc/rollout_deep.hip, threshold instance), no error word to check."""
@@ -1133,6 +1291,12 @@ def rollout_deep_goal_threshold(env_id, layers, Wm, bm, log_std, init, noise, co
     W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
                                                                      noise))
     init64, init32 = _threshold_init("rollout_deep_goal_threshold", env_id, init)
+    mz = _maze_arg("rollout_deep_goal_threshold", env_id, maze)
+    if mz is not None:
+        return _rollout_deep_maze(mz, _lib.GOAL_THRESHOLD, widths, W1, b1, Wt, bt, Wm, bm, log_std,
+                                  init, noise, states_rec, actions_rec,
+                                  goal=(0.0, 0.0, coord, threshold), rewards_rec=rewards_rec,
+                                  len_out=len_out, done_out=done_out)
     ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
                        a_dim)
     call("mepol_rollout_deep_goal_threshold", env_id, len(layers), widths, ptr(W1), ptr(b1),

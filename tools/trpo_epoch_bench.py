@@ -14,6 +14,9 @@ batch 24,000, traj_len 1200, policy 2 -> [300, 300] -> 2, cg_iters 20, kl_thresh
     python tools/trpo_epoch_bench.py --env GridGoal1Cut       GridGoal1 / MountainCarGoal with the
     python tools/trpo_epoch_bench.py --env MountainCarGoalCut goal wrapped in a one-member AnyGoal:
                                           the same episodes on the cut route, like for like
+    python tools/trpo_epoch_bench.py --env FourRoomsGoal      the goal_rl spec of that name: the
+                                          four-rooms box maze (the kernels' env 2), GridGoal1's
+                                          policies and goal
     python tools/trpo_epoch_bench.py --sampling_only          only the two sampling rows
 
 Per epoch, the median [min, max] over --reps epochs after --warmup:
@@ -52,8 +55,8 @@ GAMMA, LAMBD, KL_THRESH, CG_DAMPING = 0.995, 0.98, 0.001, 0.1
 
 
 ENVS = ("GridGoal1", "MountainCarGoal", "GridGoalAny", "MountainCarLeft", "GridGoal1Cut",
-        "MountainCarGoalCut")
-CUT_ENVS = ENVS[2:]           # sampled on the cut route
+        "MountainCarGoalCut", "FourRoomsGoal")
+CUT_ENVS = ENVS[2:6]          # sampled on the cut route
 MOUNTAINCAR_ENVS = ("MountainCarGoal", "MountainCarLeft", "MountainCarGoalCut")
 
 

@@ -638,27 +638,6 @@ static size_t rollout_mw_bytes(int64_t n, int64_t T, int h1, int a_dim) {
 // [h0][64] f64 slice (dynamic) + sh1, spart, sword (static, 6.5 KB) within 160 KB of LDS
 static constexpr int kRollMwMaxH0 = 306;
 
-template <int ENV, int GOAL = kGoalNone, typename... MZ>
-static int rollout_mw_prepare() {
-  MEPOL_HIP((max_dynamic_lds<rollout_mlp_mw_kernel<ENV, false, GOAL, MZ...>>(
-      kRollMwMaxH0 * 64 * (int)sizeof(double))));
-  return 0;
-}
-
-// Workgroups of the <ENV, GOAL> instance a CU holds at this dynamic LDS size; 0 on any error.
-template <int ENV, int GOAL, typename... MZ>
-static int rollout_mw_per_cu(size_t lds) {
-  int per_cu = 0;
-  if (rollout_mw_prepare<ENV, GOAL, MZ...>()) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &per_cu, rollout_mlp_mw_kernel<ENV, false, GOAL, MZ...>, 64 * kRollMwWaves, lds) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return per_cu;
-}
-
 // The multi-workgroup form's parts exchange partial sums every step.  Its workgroups take
 // (trajectory, part) from a dispatch-order ticket (see the kernel), which makes the exchange
 // deadlock-free whenever a trajectory's np parts fit on the device; it is chosen only when the
@@ -671,8 +650,7 @@ static int rollout_mw_per_cu(size_t lds) {
 // The occupancy asked is that of the instance that will run, env x goal kind: each has its own
 // register count.  The maze (env 2) takes no LDS (its description is a kernel argument), so the
 // LDS sizes here and the KL budget of the one-workgroup form are those of the other envs.
-static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim,
-                          int goal = kGoalNone) {
+static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim, int goal) {
   const int np = (h1 + 63) / 64;
   const char* mw = getenv("MEPOL_ROLLOUT_MW");
   if (h0 > kRollMwMaxH0 || np * a_dim > 64 || (mw && mw[0] == '0')) return 0;
@@ -681,20 +659,39 @@ static int rollout_use_mw(int env_id, int64_t n, int h0, int h1, int a_dim,
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return 0;
   const size_t lds = (size_t)h0 * 64 * sizeof(double);
-  int per_cu;
-  if (env_id == 2)
-    per_cu = goal == kGoalBall        ? rollout_mw_per_cu<2, kGoalBall, MazeArgs>(lds)
-             : goal == kGoalThreshold ? rollout_mw_per_cu<2, kGoalThreshold, MazeArgs>(lds)
-                                      : rollout_mw_per_cu<2, kGoalNone, MazeArgs>(lds);
-  else if (goal == kGoalBall)  // (env 1)
-    per_cu = rollout_mw_per_cu<1, kGoalBall>(lds);
-  else if (goal == kGoalThreshold)
-    per_cu = env_id == 0 ? rollout_mw_per_cu<0, kGoalThreshold>(lds)
-                         : rollout_mw_per_cu<1, kGoalThreshold>(lds);
-  else
-    per_cu = env_id == 0 ? rollout_mw_per_cu<0, kGoalNone>(lds)
-                         : rollout_mw_per_cu<1, kGoalNone>(lds);
+  // the instance's workgroups per CU at this dynamic LDS size; 0 on any error
+  int per_cu = 0;
+  const MazeArgs type_only{};  // (the query reads no maze)
+  rollout_instance(env_id, goal, &type_only, [&](auto E, auto G, const auto&... m) {
+    constexpr auto kernel = rollout_mlp_mw_kernel<E(), false, G(), std::decay_t<decltype(m)>...>;
+    MEPOL_HIP((max_dynamic_lds<kernel>(kRollMwMaxH0 * 64 * (int)sizeof(double))));
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64 * kRollMwWaves, lds) !=
+        hipSuccess) {
+      (void)hipGetLastError();
+      per_cu = 0;
+    }
+    return 0;
+  });
   return per_cu > 0 && n * np <= (int64_t)per_cu * cus;
+}
+
+// The answers of the four *_plan_info and *_workspace_size families behind their own argument
+// checks: the form the (env, kind) instance's occupancy gives, and the workspace of that form.
+static int rollout_plan_info(int env_id, int kind, int64_t n, int h0, int h1, int a_dim,
+                             int* workgroups_per_traj, int* k_chunks) {
+  const int mw = rollout_use_mw(env_id, n, h0, h1, a_dim, kind);
+  *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
+  *k_chunks = kRollChunks;  // both forms
+  return 0;
+}
+
+static int rollout_workspace_size(int env_id, int kind, int64_t n, int64_t T, int h0, int h1,
+                                  int a_dim, size_t* bytes) {
+  // the mail only when the multi-workgroup form would run; the error word always
+  *bytes = (n > 0 && rollout_use_mw(env_id, n, h0, h1, a_dim, kind))
+               ? rollout_mw_bytes(n, T, h1, a_dim)
+               : 256;
+  return 0;
 }
 
 extern "C" int mepol_rollout_mlp_plan_info(int64_t n, int h0, int h1, int a_dim,
@@ -705,10 +702,7 @@ extern "C" int mepol_rollout_mlp_plan_info(int64_t n, int h0, int h1, int a_dim,
     return kErrBadArg;
   }
   // (GridWorld and MountainCar kernels have the same resources: env 1 stands for both)
-  const int mw = rollout_use_mw(1, n, h0, h1, a_dim);
-  *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
-  *k_chunks = kRollChunks;  // both forms
-  return 0;
+  return rollout_plan_info(1, kGoalNone, n, h0, h1, a_dim, workgroups_per_traj, k_chunks);
 }
 
 extern "C" int mepol_rollout_mlp_workspace_size(int64_t n, int64_t T, int h0, int h1, int a_dim,
@@ -717,29 +711,7 @@ extern "C" int mepol_rollout_mlp_workspace_size(int64_t n, int64_t T, int h0, in
     set_error("mepol_rollout_mlp_workspace_size: bad arguments");
     return kErrBadArg;
   }
-  // the mail only when the multi-workgroup form would run; the error word always
-  *bytes = (n > 0 && rollout_use_mw(1, n, h0, h1, a_dim)) ? rollout_mw_bytes(n, T, h1, a_dim)
-                                                          : 256;
-  return 0;
-}
-
-template <int ENV, int GOAL = kGoalNone, typename... MZ>
-static hipError_t rollout_mw_launch(const double* W1, const double* b1, int h0,
-                                    const double* W2t, const double* b2, int h1, const double* Wm,
-                                    const double* bm, const double* log_std, int a_dim,
-                                    const double* init64, const float* init32,
-                                    const double* noise, int64_t n, int64_t T, float* states_rec,
-                                    float* actions_rec, double* visited, double* final_state,
-                                    int np, int nw, unsigned long long* mail, int* err,
-                                    int* ticket, const GoalArgs& goal, hipStream_t st,
-                                    const MZ&... mz) {
-  long long* probe = nullptr;
-  hipLaunchKernelGGL((rollout_mlp_mw_kernel<ENV, false, GOAL, MZ...>), dim3((unsigned)(n * np)),
-                     dim3(64 * kRollMwWaves), (unsigned)((size_t)h0 * 64 * sizeof(double)), st,
-                     W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T,
-                     states_rec, actions_rec, visited, final_state, np, nw, mail, err, ticket,
-                     probe, goal, mz...);
-  return hipGetLastError();
+  return rollout_workspace_size(1, kGoalNone, n, T, h0, h1, a_dim, bytes);
 }
 
 // mepol_rollout_mlp_plan_info for mepol_rollout_goal: the goal-mode instance's own occupancy
@@ -751,26 +723,20 @@ extern "C" int mepol_rollout_goal_plan_info(int64_t n, int h0, int h1, int a_dim
     set_error("mepol_rollout_goal_plan_info: bad arguments");
     return kErrBadArg;
   }
-  const int mw = rollout_use_mw(1, n, h0, h1, a_dim, kGoalBall);
-  *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
-  *k_chunks = kRollChunks;  // both forms
-  return 0;
+  return rollout_plan_info(1, kGoalBall, n, h0, h1, a_dim, workgroups_per_traj, k_chunks);
 }
 
-// mepol_rollout_mlp (goal == nullptr), mepol_rollout_goal (kind kGoalBall, env 1) and
-// mepol_rollout_goal_threshold (kind kGoalThreshold) behind their argument checks: the same
-// choice of form, workspace layout and launches, the kernels' GOAL instances for the last two.
+// mepol_rollout_mlp (kind kGoalNone, ga unused), mepol_rollout_goal (kGoalBall, env 1) and
+// mepol_rollout_goal_threshold (kGoalThreshold) behind their argument checks: the same choice of
+// form, workspace layout and launches, the kernels' GOAL instances for the last two.
 // env_id 2 (mepol_rollout_maze, any kind): the ENV = 2 instances with *mz, already validated.
-static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h0,
-                           const double* W2t, const double* b2, int h1, const double* Wm,
-                           const double* bm, const double* log_std, int a_dim,
+static int rollout_mlp_run(int env_id, int kind, const GoalArgs& ga, const double* W1,
+                           const double* b1, int h0, const double* W2t, const double* b2, int h1,
+                           const double* Wm, const double* bm, const double* log_std, int a_dim,
                            const double* init64, const float* init32, const double* noise,
                            int64_t n, int64_t T, float* states_rec, float* actions_rec,
-                           double* visited, double* final_state, const GoalArgs* goal,
-                           void* workspace, size_t workspace_bytes, void* stream,
-                           int kind = kGoalBall, const MazeArgs* mz = nullptr) {
-  const GoalArgs ga = goal ? *goal : GoalArgs{};
-  if (!goal) kind = kGoalNone;
+                           double* visited, double* final_state, void* workspace,
+                           size_t workspace_bytes, void* stream, const MazeArgs* mz = nullptr) {
   const int threads = ((h0 > h1 ? h0 : h1) + 63) / 64 * 64;
   hipStream_t st = (hipStream_t)stream;
   int* err = (int*)workspace;
@@ -785,25 +751,17 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
       MEPOL_HIP(hipMemsetAsync(ticket, 0, sizeof(int), st));
       // every mail word starts as kMailEmpty (all ones)
       MEPOL_HIP(hipMemsetAsync(mail, 0xff, (size_t)n * T * np * a_dim * 8, st));
-#define MEPOL_ROLL_MW(E, G)                                                                      \
-  rollout_mw_launch<E, G>(W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, \
-                          n, T, states_rec, actions_rec, visited, final_state, np, nw, mail, err, \
-                          ticket, ga, st)
-#define MEPOL_ROLL_MW_MAZE(G)                                                                     \
-  rollout_mw_launch<2, G, MazeArgs>(W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64,      \
-                                    init32, noise, n, T, states_rec, actions_rec, visited,        \
-                                    final_state, np, nw, mail, err, ticket, ga, st, *mz)
-      const hipError_t e =
-          env_id == 2 ? (kind == kGoalBall        ? MEPOL_ROLL_MW_MAZE(kGoalBall)
-                         : kind == kGoalThreshold ? MEPOL_ROLL_MW_MAZE(kGoalThreshold)
-                                                  : MEPOL_ROLL_MW_MAZE(kGoalNone))
-          : kind == kGoalBall ? MEPOL_ROLL_MW(1, kGoalBall)
-          : kind == kGoalThreshold
-              ? (env_id == 0 ? MEPOL_ROLL_MW(0, kGoalThreshold) : MEPOL_ROLL_MW(1, kGoalThreshold))
-              : (env_id == 0 ? MEPOL_ROLL_MW(0, kGoalNone) : MEPOL_ROLL_MW(1, kGoalNone));
-#undef MEPOL_ROLL_MW
-#undef MEPOL_ROLL_MW_MAZE
-      if (e == hipSuccess) return 0;
+      const int e = rollout_instance(env_id, kind, mz, [&](auto E, auto G, const auto&... m) {
+        long long* probe = nullptr;
+        hipLaunchKernelGGL(
+            (rollout_mlp_mw_kernel<E(), false, G(), std::decay_t<decltype(m)>...>),
+            dim3((unsigned)(n * np)), dim3(64 * kRollMwWaves),
+            (unsigned)((size_t)h0 * 64 * sizeof(double)), st, W1, b1, h0, W2t, b2, h1, Wm, bm,
+            log_std, a_dim, init64, init32, noise, n, T, states_rec, actions_rec, visited,
+            final_state, np, nw, mail, err, ticket, probe, ga, m...);
+        return (int)hipGetLastError();
+      });
+      if (e == 0) return 0;
       (void)hipGetLastError();  // launch refused: the one-workgroup form
     }
   }
@@ -814,40 +772,15 @@ static int rollout_mlp_run(int env_id, const double* W1, const double* b1, int h
   if (klv) KL = std::min(KL, atoi(klv));
   KL = std::max(0, std::min(KL, h0));
   const size_t lds = (size_t)KL * threads * sizeof(double);
-#define MEPOL_ROLL(E, U, G)                                                                       \
-  do {                                                                                            \
-    MEPOL_HIP((max_dynamic_lds<rollout_mlp_kernel<E, U, G>>(150 * 1024)));                        \
-    hipLaunchKernelGGL((rollout_mlp_kernel<E, U, G>), g, dim3(threads), lds, st, W1, b1, h0, W2t, \
-                       b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T, states_rec,   \
-                       actions_rec, visited, final_state, KL, ga);                                \
-  } while (0)
-#define MEPOL_ROLL_MAZE(G)                                                                        \
-  do {                                                                                            \
-    MEPOL_HIP((max_dynamic_lds<rollout_mlp_kernel<2, 8, G, MazeArgs>>(150 * 1024)));              \
-    hipLaunchKernelGGL((rollout_mlp_kernel<2, 8, G, MazeArgs>), g, dim3(threads), lds, st, W1, b1, \
-                       h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32, noise, n, T,      \
-                       states_rec, actions_rec, visited, final_state, KL, ga, *mz);               \
-  } while (0)
-  if (env_id == 2 && kind == kGoalBall)
-    MEPOL_ROLL_MAZE(kGoalBall);
-  else if (env_id == 2 && kind == kGoalThreshold)
-    MEPOL_ROLL_MAZE(kGoalThreshold);
-  else if (env_id == 2)
-    MEPOL_ROLL_MAZE(kGoalNone);
-  else if (kind == kGoalBall)
-    MEPOL_ROLL(1, 8, kGoalBall);
-  else if (kind == kGoalThreshold && env_id == 0)
-    MEPOL_ROLL(0, 8, kGoalThreshold);
-  else if (kind == kGoalThreshold)
-    MEPOL_ROLL(1, 8, kGoalThreshold);
-  else if (env_id == 0)
-    MEPOL_ROLL(0, 8, kGoalNone);
-  else
-    MEPOL_ROLL(1, 8, kGoalNone);
-#undef MEPOL_ROLL
-#undef MEPOL_ROLL_MAZE
-  MEPOL_CHECK_LAUNCH();
-  return 0;
+  return rollout_instance(env_id, kind, mz, [&](auto E, auto G, const auto&... m) {
+    constexpr auto kernel = rollout_mlp_kernel<E(), 8, G(), std::decay_t<decltype(m)>...>;
+    MEPOL_HIP((max_dynamic_lds<kernel>(150 * 1024)));
+    hipLaunchKernelGGL(kernel, g, dim3(threads), lds, st, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std,
+                       a_dim, init64, init32, noise, n, T, states_rec, actions_rec, visited,
+                       final_state, KL, ga, m...);
+    MEPOL_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int mepol_rollout_mlp(int env_id, const double* W1, const double* b1, int h0,
@@ -867,9 +800,9 @@ extern "C" int mepol_rollout_mlp(int env_id, const double* W1, const double* b1,
               kRollMaxA);
     return kErrBadArg;
   }
-  return rollout_mlp_run(env_id, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32,
-                         noise, n, T, states_rec, actions_rec, visited, final_state, nullptr,
-                         workspace, workspace_bytes, stream);
+  return rollout_mlp_run(env_id, kGoalNone, GoalArgs{}, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std,
+                         a_dim, init64, init32, noise, n, T, states_rec, actions_rec, visited,
+                         final_state, workspace, workspace_bytes, stream);
 }
 
 // The goal-mode workspace: the same layout as mepol_rollout_mlp's, sized by the goal-mode
@@ -885,10 +818,7 @@ extern "C" int mepol_rollout_goal_workspace_size(int env_id, int64_t n, int64_t 
     set_error("mepol_rollout_goal: only GridWorld (env_id 1) has a goal mode");
     return kErrUnsupported;
   }
-  *bytes = (n > 0 && rollout_use_mw(1, n, h0, h1, a_dim, kGoalBall))
-               ? rollout_mw_bytes(n, T, h1, a_dim)
-               : 256;
-  return 0;
+  return rollout_workspace_size(1, kGoalBall, n, T, h0, h1, a_dim, bytes);
 }
 
 extern "C" int mepol_rollout_goal(int env_id, const double* W1, const double* b1, int h0,
@@ -914,9 +844,9 @@ extern "C" int mepol_rollout_goal(int env_id, const double* W1, const double* b1
     return kErrUnsupported;
   }
   const GoalArgs goal{{goal_x}, goal_y, {radius}, rewards_rec, len_out, done_out};
-  return rollout_mlp_run(1, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, nullptr, init32,
-                         noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
-                         workspace_bytes, stream);
+  return rollout_mlp_run(1, kGoalBall, goal, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim,
+                         nullptr, init32, noise, n, T, states_rec, actions_rec, nullptr, nullptr,
+                         workspace, workspace_bytes, stream);
 }
 
 // ---- threshold goals (either env) -------------------------------------------------------------
@@ -935,10 +865,8 @@ extern "C" int mepol_rollout_goal_threshold_plan_info(int env_id, int64_t n, int
               "env 1 with a_dim = 2, hidden <= %d)", kRollMaxH);
     return kErrBadArg;
   }
-  const int mw = rollout_use_mw(env_id, n, h0, h1, a_dim, kGoalThreshold);
-  *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
-  *k_chunks = kRollChunks;  // both forms
-  return 0;
+  return rollout_plan_info(env_id, kGoalThreshold, n, h0, h1, a_dim, workgroups_per_traj,
+                           k_chunks);
 }
 
 extern "C" int mepol_rollout_goal_threshold_workspace_size(int env_id, int64_t n, int64_t T,
@@ -949,10 +877,7 @@ extern "C" int mepol_rollout_goal_threshold_workspace_size(int env_id, int64_t n
               "or env 1 with a_dim = 2, hidden <= %d)", kRollMaxH);
     return kErrBadArg;
   }
-  *bytes = (n > 0 && rollout_use_mw(env_id, n, h0, h1, a_dim, kGoalThreshold))
-               ? rollout_mw_bytes(n, T, h1, a_dim)
-               : 256;
-  return 0;
+  return rollout_workspace_size(env_id, kGoalThreshold, n, T, h0, h1, a_dim, bytes);
 }
 
 extern "C" int mepol_rollout_goal_threshold(
@@ -973,9 +898,9 @@ extern "C" int mepol_rollout_goal_threshold(
     return kErrBadArg;
   }
   const GoalArgs goal = threshold_goal(coord, threshold, rewards_rec, len_out, done_out);
-  return rollout_mlp_run(env_id, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, init64, init32,
-                         noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
-                         workspace_bytes, stream, kGoalThreshold);
+  return rollout_mlp_run(env_id, kGoalThreshold, goal, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std,
+                         a_dim, init64, init32, noise, n, T, states_rec, actions_rec, nullptr,
+                         nullptr, workspace, workspace_bytes, stream);
 }
 
 // ---- box mazes (env 2) -------------------------------------------------------------------------
@@ -1015,12 +940,8 @@ extern "C" int mepol_rollout_step_maze(const mepol_maze* maze, float* env_f32, c
   return 0;
 }
 
-static bool maze_kind_ok(int goal_kind) {
-  return goal_kind == kGoalNone || goal_kind == kGoalBall || goal_kind == kGoalThreshold;
-}
-
 static bool maze_shape_ok(int goal_kind, int h0, int h1, int a_dim) {
-  return maze_kind_ok(goal_kind) && h0 > 0 && h1 > 0 && h0 <= kRollMaxH && h1 <= kRollMaxH &&
+  return goal_kind_ok(goal_kind) && h0 > 0 && h1 > 0 && h0 <= kRollMaxH && h1 <= kRollMaxH &&
          a_dim == 2;
 }
 
@@ -1031,10 +952,7 @@ extern "C" int mepol_rollout_maze_plan_info(int goal_kind, int64_t n, int h0, in
               "<= %d)", kRollMaxH);
     return kErrBadArg;
   }
-  const int mw = rollout_use_mw(2, n, h0, h1, a_dim, goal_kind);
-  *workgroups_per_traj = mw ? (h1 + 63) / 64 : 1;
-  *k_chunks = kRollChunks;  // both forms
-  return 0;
+  return rollout_plan_info(2, goal_kind, n, h0, h1, a_dim, workgroups_per_traj, k_chunks);
 }
 
 extern "C" int mepol_rollout_maze_workspace_size(int goal_kind, int64_t n, int64_t T, int h0,
@@ -1044,10 +962,7 @@ extern "C" int mepol_rollout_maze_workspace_size(int goal_kind, int64_t n, int64
               "hidden <= %d)", kRollMaxH);
     return kErrBadArg;
   }
-  *bytes = (n > 0 && rollout_use_mw(2, n, h0, h1, a_dim, goal_kind))
-               ? rollout_mw_bytes(n, T, h1, a_dim)
-               : 256;
-  return 0;
+  return rollout_workspace_size(2, goal_kind, n, T, h0, h1, a_dim, bytes);
 }
 
 extern "C" int mepol_rollout_maze(const mepol_maze* maze, int goal_kind, const double* W1,
@@ -1060,11 +975,9 @@ extern "C" int mepol_rollout_maze(const mepol_maze* maze, int goal_kind, const d
                                   float* rewards_rec, int32_t* len_out, int32_t* done_out,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   if (!maze_args_ok(maze, "mepol_rollout_maze")) return kErrBadArg;
-  const bool goal_ok =
-      goal_kind == kGoalNone ||
-      (rewards_rec && len_out && done_out && T <= INT32_MAX &&
-       (goal_kind == kGoalBall ? goal_x == goal_x && goal_y == goal_y && goal_value >= 0.0
-                               : (coord == 0 || coord == 1) && goal_value == goal_value));
+  GoalArgs goal;
+  const bool goal_ok = goal_from_kind(goal_kind, goal_x, goal_y, coord, goal_value, T, rewards_rec,
+                                      len_out, done_out, &goal);
   if (!maze_shape_ok(goal_kind, h0, h1, a_dim) || !goal_ok || !init32 || !W1 || !b1 || !W2t ||
       !b2 || !Wm || !bm || !log_std || !noise || !states_rec || !actions_rec ||
       (workspace && workspace_bytes < sizeof(int))) {
@@ -1074,13 +987,7 @@ extern "C" int mepol_rollout_maze(const mepol_maze* maze, int goal_kind, const d
     return kErrBadArg;
   }
   if (n <= 0 || T <= 0) return 0;
-  GoalArgs goal{};
-  if (goal_kind == kGoalBall)
-    goal = GoalArgs{{goal_x}, goal_y, {goal_value}, rewards_rec, len_out, done_out};
-  else if (goal_kind == kGoalThreshold)
-    goal = threshold_goal(coord, goal_value, rewards_rec, len_out, done_out);
-  return rollout_mlp_run(2, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim, nullptr, init32,
-                         noise, n, T, states_rec, actions_rec, visited, final_state,
-                         goal_kind == kGoalNone ? nullptr : &goal, workspace, workspace_bytes,
-                         stream, goal_kind, maze);
+  return rollout_mlp_run(2, goal_kind, goal, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std, a_dim,
+                         nullptr, init32, noise, n, T, states_rec, actions_rec, visited,
+                         final_state, workspace, workspace_bytes, stream, maze);
 }

@@ -310,70 +310,51 @@ static DeepPlan deep_plan(int n_hidden, const int* widths) {
   return p;
 }
 
-// mepol_rollout_deep (goal == nullptr), mepol_rollout_deep_goal (kind kGoalBall, env 1) and
-// mepol_rollout_deep_goal_threshold (kind kGoalThreshold) behind their argument checks: the same
+// mepol_rollout_deep (kind kGoalNone, ga unused), mepol_rollout_deep_goal (kGoalBall, env 1) and
+// mepol_rollout_deep_goal_threshold (kGoalThreshold) behind their argument checks: the same
 // plan, workspace header and launch, the kernel's GOAL instances for the last two.  env_id 2
 // (mepol_rollout_deep_maze, any kind): the ENV = 2 instances with *mz, already validated.
-static int deep_run(int env_id, int n_hidden, const int* widths, const double* W1,
-                    const double* b1, const double* Wt, const double* bt, const double* Wm,
-                    const double* bm, const double* log_std, int a_dim, const double* init64,
-                    const float* init32, const double* noise, int64_t n, int64_t T,
-                    float* states_rec, float* actions_rec, double* visited, double* final_state,
-                    const GoalArgs* goal, void* workspace, void* stream, int kind = kGoalBall,
+static int deep_run(int env_id, int kind, const GoalArgs& ga, int n_hidden, const int* widths,
+                    const double* W1, const double* b1, const double* Wt, const double* bt,
+                    const double* Wm, const double* bm, const double* log_std, int a_dim,
+                    const double* init64, const float* init32, const double* noise, int64_t n,
+                    int64_t T, float* states_rec, float* actions_rec, double* visited,
+                    double* final_state, void* workspace, void* stream,
                     const MazeArgs* mz = nullptr) {
   const DeepPlan p = deep_plan(n_hidden, widths);
-  const GoalArgs ga = goal ? *goal : GoalArgs{};
-  if (!goal) kind = kGoalNone;
   hipStream_t st = (hipStream_t)stream;
   if (workspace) MEPOL_HIP(hipMemsetAsync(workspace, 0, kDeepWorkspaceBytes, st));
   const dim3 g((unsigned)n), b(p.threads);
-#define MEPOL_DEEP(E, G)                                                                          \
-  do {                                                                                            \
-    MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<E, G>>(kDeepLdsBytes)));                       \
-    hipLaunchKernelGGL((rollout_deep_kernel<E, G>), g, b, p.lds, st, W1, b1, Wt, bt, Wm, bm,      \
-                       log_std, a_dim, init64, init32, noise, n, T, states_rec, actions_rec,      \
-                       visited, final_state, p.sh, ga);                                           \
-  } while (0)
-#define MEPOL_DEEP_MAZE(G)                                                                        \
-  do {                                                                                            \
-    MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<2, G, MazeArgs>>(kDeepLdsBytes)));             \
-    hipLaunchKernelGGL((rollout_deep_kernel<2, G, MazeArgs>), g, b, p.lds, st, W1, b1, Wt, bt, Wm, \
-                       bm, log_std, a_dim, init64, init32, noise, n, T, states_rec, actions_rec,  \
-                       visited, final_state, p.sh, ga, *mz);                                      \
-  } while (0)
-  if (env_id == 2 && kind == kGoalBall)
-    MEPOL_DEEP_MAZE(kGoalBall);
-  else if (env_id == 2 && kind == kGoalThreshold)
-    MEPOL_DEEP_MAZE(kGoalThreshold);
-  else if (env_id == 2)
-    MEPOL_DEEP_MAZE(kGoalNone);
-  else if (kind == kGoalBall)
-    MEPOL_DEEP(1, kGoalBall);
-  else if (kind == kGoalThreshold && env_id == 0)
-    MEPOL_DEEP(0, kGoalThreshold);
-  else if (kind == kGoalThreshold)
-    MEPOL_DEEP(1, kGoalThreshold);
-  else if (env_id == 0)
-    MEPOL_DEEP(0, kGoalNone);
-  else
-    MEPOL_DEEP(1, kGoalNone);
-#undef MEPOL_DEEP
-#undef MEPOL_DEEP_MAZE
-  MEPOL_CHECK_LAUNCH();
-  return 0;
+  return rollout_instance(env_id, kind, mz, [&](auto E, auto G, const auto&... m) {
+    constexpr auto kernel = rollout_deep_kernel<E(), G(), std::decay_t<decltype(m)>...>;
+    MEPOL_HIP((max_dynamic_lds<kernel>(kDeepLdsBytes)));
+    hipLaunchKernelGGL(kernel, g, b, p.lds, st, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, init64,
+                       init32, noise, n, T, states_rec, actions_rec, visited, final_state, p.sh, ga,
+                       m...);
+    MEPOL_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
-// Workgroups of the <ENV, GOAL> instance the device holds at once for this shape: the kernel's
-// occupancy at the block size and dynamic LDS the launcher chooses, times the CU count.
-template <int ENV, int GOAL, typename... MZ>
-static int deep_resident(int n_hidden, const int* widths, int* resident_workgroups) {
+// The deep *_plan_info entry points behind their own argument checks: workgroups of the
+// (env, kind) instance the device holds at once for this shape, the kernel's occupancy at the
+// block size and dynamic LDS the launcher chooses, times the CU count.
+static int deep_resident(int env_id, int kind, int n_hidden, const int* widths,
+                         int* resident_workgroups) {
   const DeepPlan p = deep_plan(n_hidden, widths);
   int dev = 0, cus = 0, per_cu = 0;
   MEPOL_HIP(hipGetDevice(&dev));
   MEPOL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  MEPOL_HIP((max_dynamic_lds<rollout_deep_kernel<ENV, GOAL, MZ...>>(kDeepLdsBytes)));
-  MEPOL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, rollout_deep_kernel<ENV, GOAL, MZ...>, (int)p.threads, p.lds));
+  const MazeArgs type_only{};  // (the query reads no maze)
+  const int rc =
+      rollout_instance(env_id, kind, &type_only, [&](auto E, auto G, const auto&... m) {
+        constexpr auto kernel = rollout_deep_kernel<E(), G(), std::decay_t<decltype(m)>...>;
+        MEPOL_HIP((max_dynamic_lds<kernel>(kDeepLdsBytes)));
+        MEPOL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)p.threads,
+                                                               p.lds));
+        return 0;
+      });
+  if (rc) return rc;
   *resident_workgroups = per_cu * cus;
   return 0;
 }
@@ -410,9 +391,9 @@ extern "C" int mepol_rollout_deep(int env_id, int n_hidden, const int* widths, c
               kDeepWorkspaceBytes);
     return kErrWorkspace;
   }
-  return deep_run(env_id, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, init64, init32,
-                  noise, n, T, states_rec, actions_rec, visited, final_state, nullptr, workspace,
-                  stream);
+  return deep_run(env_id, kGoalNone, GoalArgs{}, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std,
+                  a_dim, init64, init32, noise, n, T, states_rec, actions_rec, visited,
+                  final_state, workspace, stream);
 }
 
 // Workgroups (= trajectories) of mepol_rollout_deep itself the device holds at once: the
@@ -422,8 +403,7 @@ extern "C" int mepol_rollout_deep_plan_info(int env_id, int n_hidden, const int*
                                             int* resident_workgroups) {
   if (!resident_workgroups || !deep_shape_ok(env_id, n_hidden, widths, a_dim))
     return deep_bad_args("mepol_rollout_deep_plan_info");
-  return env_id == 0 ? deep_resident<0, kGoalNone>(n_hidden, widths, resident_workgroups)
-                     : deep_resident<1, kGoalNone>(n_hidden, widths, resident_workgroups);
+  return deep_resident(env_id, kGoalNone, n_hidden, widths, resident_workgroups);
 }
 
 // mepol_rollout_deep on GridWorld with early termination at a goal: mepol_rollout_goal's episode
@@ -458,9 +438,9 @@ extern "C" int mepol_rollout_deep_goal(int env_id, int n_hidden, const int* widt
     return kErrWorkspace;
   }
   const GoalArgs goal{{goal_x}, goal_y, {radius}, rewards_rec, len_out, done_out};
-  return deep_run(1, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, nullptr, init32,
-                  noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace,
-                  stream);
+  return deep_run(1, kGoalBall, goal, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim,
+                  nullptr, init32, noise, n, T, states_rec, actions_rec, nullptr, nullptr,
+                  workspace, stream);
 }
 
 // Workgroups of the goal-mode instance the device holds at once for this shape: the kernel's
@@ -474,7 +454,7 @@ extern "C" int mepol_rollout_deep_goal_plan_info(int n_hidden, const int* widths
               kDeepMinL, kDeepMaxL, kDeepMaxH);
     return kErrBadArg;
   }
-  return deep_resident<1, kGoalBall>(n_hidden, widths, resident_workgroups);
+  return deep_resident(1, kGoalBall, n_hidden, widths, resident_workgroups);
 }
 
 // mepol_rollout_deep_goal with the threshold test of mepol_rollout_goal_threshold, on either env.
@@ -502,9 +482,9 @@ extern "C" int mepol_rollout_deep_goal_threshold(
     return kErrWorkspace;
   }
   const GoalArgs goal = threshold_goal(coord, threshold, rewards_rec, len_out, done_out);
-  return deep_run(env_id, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, init64, init32,
-                  noise, n, T, states_rec, actions_rec, nullptr, nullptr, &goal, workspace, stream,
-                  kGoalThreshold);
+  return deep_run(env_id, kGoalThreshold, goal, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std,
+                  a_dim, init64, init32, noise, n, T, states_rec, actions_rec, nullptr, nullptr,
+                  workspace, stream);
 }
 
 // mepol_rollout_deep_goal_plan_info for the threshold instance of this env.
@@ -518,8 +498,7 @@ extern "C" int mepol_rollout_deep_goal_threshold_plan_info(int env_id, int n_hid
               kDeepMinL, kDeepMaxL, kDeepMaxH);
     return kErrBadArg;
   }
-  return env_id == 0 ? deep_resident<0, kGoalThreshold>(n_hidden, widths, resident_workgroups)
-                     : deep_resident<1, kGoalThreshold>(n_hidden, widths, resident_workgroups);
+  return deep_resident(env_id, kGoalThreshold, n_hidden, widths, resident_workgroups);
 }
 
 // ---- box mazes (env 2) -------------------------------------------------------------------------
@@ -534,8 +513,7 @@ static int deep_maze_bad_args(const char* who) {
 }
 
 static bool deep_maze_shape_ok(int goal_kind, int n_hidden, const int* widths, int a_dim) {
-  return (goal_kind == kGoalNone || goal_kind == kGoalBall || goal_kind == kGoalThreshold) &&
-         a_dim == 2 && deep_shape_ok(1, n_hidden, widths, a_dim);
+  return goal_kind_ok(goal_kind) && a_dim == 2 && deep_shape_ok(1, n_hidden, widths, a_dim);
 }
 
 extern "C" int mepol_rollout_deep_maze_workspace_size(int64_t n, int64_t T, int n_hidden,
@@ -551,11 +529,7 @@ extern "C" int mepol_rollout_deep_maze_plan_info(int goal_kind, int n_hidden, co
                                                  int a_dim, int* resident_workgroups) {
   if (!resident_workgroups || !deep_maze_shape_ok(goal_kind, n_hidden, widths, a_dim))
     return deep_maze_bad_args("mepol_rollout_deep_maze_plan_info");
-  return goal_kind == kGoalBall
-             ? deep_resident<2, kGoalBall, MazeArgs>(n_hidden, widths, resident_workgroups)
-         : goal_kind == kGoalThreshold
-             ? deep_resident<2, kGoalThreshold, MazeArgs>(n_hidden, widths, resident_workgroups)
-             : deep_resident<2, kGoalNone, MazeArgs>(n_hidden, widths, resident_workgroups);
+  return deep_resident(2, goal_kind, n_hidden, widths, resident_workgroups);
 }
 
 extern "C" int mepol_rollout_deep_maze(
@@ -566,11 +540,9 @@ extern "C" int mepol_rollout_deep_maze(
     float* actions_rec, double* visited, double* final_state, float* rewards_rec,
     int32_t* len_out, int32_t* done_out, void* workspace, size_t workspace_bytes, void* stream) {
   if (!maze_args_ok(maze, "mepol_rollout_deep_maze")) return kErrBadArg;
-  const bool goal_ok =
-      goal_kind == kGoalNone ||
-      (rewards_rec && len_out && done_out && T <= INT32_MAX &&
-       (goal_kind == kGoalBall ? goal_x == goal_x && goal_y == goal_y && goal_value >= 0.0
-                               : (coord == 0 || coord == 1) && goal_value == goal_value));
+  GoalArgs goal;
+  const bool goal_ok = goal_from_kind(goal_kind, goal_x, goal_y, coord, goal_value, T, rewards_rec,
+                                      len_out, done_out, &goal);
   if (!deep_maze_shape_ok(goal_kind, n_hidden, widths, a_dim) || !goal_ok || !init32 || !W1 ||
       !b1 || !Wt || !bt || !Wm || !bm || !log_std || !noise || !states_rec || !actions_rec)
     return deep_maze_bad_args("mepol_rollout_deep_maze");
@@ -580,12 +552,7 @@ extern "C" int mepol_rollout_deep_maze(
     return kErrWorkspace;
   }
   if (n <= 0 || T <= 0) return 0;
-  GoalArgs goal{};
-  if (goal_kind == kGoalBall)
-    goal = GoalArgs{{goal_x}, goal_y, {goal_value}, rewards_rec, len_out, done_out};
-  else if (goal_kind == kGoalThreshold)
-    goal = threshold_goal(coord, goal_value, rewards_rec, len_out, done_out);
-  return deep_run(2, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim, nullptr, init32,
-                  noise, n, T, states_rec, actions_rec, visited, final_state,
-                  goal_kind == kGoalNone ? nullptr : &goal, workspace, stream, goal_kind, maze);
+  return deep_run(2, goal_kind, goal, n_hidden, widths, W1, b1, Wt, bt, Wm, bm, log_std, a_dim,
+                  nullptr, init32, noise, n, T, states_rec, actions_rec, visited, final_state,
+                  workspace, stream, maze);
 }

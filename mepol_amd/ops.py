@@ -874,60 +874,29 @@ def rollout_mlp(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, states_rec
     """All T steps of a batched MountainCar (env_id 0, init f64 [n,2]) / GridWorld (1, init f32) /
     box maze (2, init f32, with maze=) rollout with the 2-hidden-layer ReLU policy in one launch;
     noise [T, n, a] f64."""
-    T, n, a_dim = noise.shape
-    h0, h1 = W1.shape[0], W2.shape[0]
-    W2t = W2.t().contiguous()
     mz = _maze_arg("rollout_mlp", env_id, maze)
-    if mz is not None:
-        return _rollout_maze(mz, _lib.GOAL_NONE, W1, b1, W2t, b2, Wm, bm, log_std, init, noise,
-                             states_rec, actions_rec, visited=visited)
-    init64 = init.contiguous() if env_id == 0 else None
-    init32 = init.contiguous() if env_id == 1 else None
-    ws = _ws_or_cached(None, init.device, "rollout", "rollout_mlp", n, T, h0, h1, a_dim)
-    args = (env_id, ptr(W1.contiguous()), ptr(b1), h0, ptr(W2t), ptr(b2), h1,
-            ptr(Wm.contiguous()), ptr(bm), ptr(log_std.contiguous()), a_dim, ptr(init64),
-            ptr(init32), ptr(noise.contiguous()), n, T, ptr(states_rec), ptr(actions_rec),
-            ptr(visited), None)
-    call("mepol_rollout_mlp", *args, ptr(ws), ws.numel(), _stream())
-    # word 0 (zeroed by the call): the multi-workgroup form gave up waiting for a part of a
-    # trajectory.  The one-workgroup form (no workspace) sums in the same order and rewrites
-    # every output, so the result is the same bits either way.
-    if int(ws[:4].view(torch.int32)[0].item()) != 0:
-        import warnings
-
-        warnings.warn("mepol_rollout_mlp: workgroups of a trajectory were not co-resident; "
-                      "re-ran the one-workgroup form")
-        call("mepol_rollout_mlp", *args, None, 0, _stream())
+    _rollout_two_layer(env_id, mz, _lib.GOAL_NONE, W1, b1, W2.t().contiguous(), b2, Wm, bm,
+                       log_std, init, noise, states_rec, actions_rec, visited=visited)
 
 
-def _rollout_maze(mz, kind, W1, b1, W2t, b2, Wm, bm, log_std, init, noise, states_rec, actions_rec,
-                  visited=None, goal=(0.0, 0.0, 0, 0.0), rewards_rec=None, len_out=None,
-                  done_out=None, defer_check=False):
-    """mepol_rollout_maze behind the two-layer wrappers' own checks: goal = (x, y, coord, value).
-    The error word is handled as the wrapper that called does: re-run at once (returns None), or
-    with defer_check (err, rerun)."""
-    T, n, a_dim = noise.shape
-    h0, h1 = W1.shape[0], W2t.shape[1]
-    if init.dtype != torch.float32:
-        raise ValueError("a box maze's init is f32 [n, 2]")
-    # (contiguous copies stay referenced until the launch is queued)
-    W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
-                                                                          log_std, init, noise))
-    ws = _ws_or_cached(None, init.device, "rollout", "rollout_maze", kind, n, T, h0, h1, a_dim)
-    gx, gy, coord, value = goal
-    args = (mz, kind, ptr(W1), ptr(b1), h0, ptr(W2t), ptr(b2), h1, ptr(Wm), ptr(bm), ptr(log_std),
-            a_dim, ptr(init), ptr(noise), n, T, float(gx), float(gy), int(coord), float(value),
-            ptr(states_rec), ptr(actions_rec), ptr(visited), None, ptr(rewards_rec), ptr(len_out),
-            ptr(done_out))
-    keep = (W1, b1, W2t, b2, Wm, bm, log_std, init, noise)
-    call("mepol_rollout_maze", *args, ptr(ws), ws.numel(), _stream())
+_NO_GOAL = (0.0, 0.0, 0, 0.0)  # (x, y, coord, value) of the entry points that take all four
+
+
+def _rollout_mw(name, args, keep, ws, n, T, defer_check):
+    """Calls the two-layer entry point `name` with its workspace and handles the error word, word
+    0 (zeroed by the call): the multi-workgroup form gave up waiting for a part of a trajectory.
+    The one-workgroup form (no workspace) sums in the same order and rewrites every output, so
+    the result is the same bits either way: warn and re-run it (returns None), or with
+    defer_check return (err, rerun) for the caller to do so.  `keep` holds the tensors behind
+    `args` until the re-run."""
+    call(name, *args, ptr(ws), ws.numel(), _stream())
 
     def rerun(_keep=keep):
         import warnings
 
-        warnings.warn("mepol_rollout_maze: workgroups of a trajectory were not co-resident; "
+        warnings.warn(f"{name}: workgroups of a trajectory were not co-resident; "
                       "re-ran the one-workgroup form")
-        call("mepol_rollout_maze", *args, None, 0, _stream())
+        call(name, *args, None, 0, _stream())
 
     err = ws[:4].view(torch.int32)
     if defer_check:
@@ -937,20 +906,143 @@ def _rollout_maze(mz, kind, W1, b1, W2t, b2, Wm, bm, log_std, init, noise, state
     return None
 
 
-def _rollout_deep_maze(mz, kind, widths, W1, b1, Wt, bt, Wm, bm, log_std, init, noise, states_rec,
-                       actions_rec, visited=None, goal=(0.0, 0.0, 0, 0.0), rewards_rec=None,
-                       len_out=None, done_out=None):
-    """mepol_rollout_deep_maze behind the deep wrappers' own checks: goal = (x, y, coord, value)."""
+def _rollout_two_layer(env_id, mz, kind, W1, b1, W2t, b2, Wm, bm, log_std, init, noise,
+                       states_rec, actions_rec, visited=None, goal=_NO_GOAL,
+                       goal_out=(None, None, None), defer_check=False):
+    """The two-layer rollouts behind the wrappers' own checks: the C entry point of this
+    (env_id, goal kind) -- mepol_rollout_maze with mz (env_id 2), else mepol_rollout_mlp,
+    mepol_rollout_goal (ball) or mepol_rollout_goal_threshold -- its workspace and the error
+    word (_rollout_mw).  goal = (x, y, coord, value), goal_out = (rewards_rec, len_out,
+    done_out)."""
     T, n, a_dim = noise.shape
-    if init.dtype != torch.float32:
+    h0, h1 = W1.shape[0], W2t.shape[1]
+    if mz is not None and init.dtype != torch.float32:
         raise ValueError("a box maze's init is f32 [n, 2]")
-    ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep_maze", n, T, len(widths),
-                       widths, a_dim)
+    # (contiguous copies stay referenced until the launch is queued)
+    W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
+                                                                          log_std, init, noise))
     gx, gy, coord, value = goal
-    call("mepol_rollout_deep_maze", mz, kind, len(widths), widths, ptr(W1), ptr(b1), ptr(Wt),
-         ptr(bt), ptr(Wm), ptr(bm), ptr(log_std), a_dim, ptr(init), ptr(noise), n, T, float(gx),
-         float(gy), int(coord), float(value), ptr(states_rec), ptr(actions_rec), ptr(visited), None,
-         ptr(rewards_rec), ptr(len_out), ptr(done_out), ptr(ws), ws.numel(), _stream())
+    policy = (ptr(W1), ptr(b1), h0, ptr(W2t), ptr(b2), h1, ptr(Wm), ptr(bm), ptr(log_std), a_dim)
+    init64, init32 = (ptr(init) if env_id == e else None for e in (0, 1))
+    batch, recs = (ptr(noise), n, T), (ptr(states_rec), ptr(actions_rec))
+    outs = tuple(ptr(t) for t in goal_out)
+    if mz is not None:
+        name, sizes = "mepol_rollout_maze", (kind, n, T, h0, h1, a_dim)
+        args = (mz, kind, *policy, ptr(init), *batch, float(gx), float(gy), int(coord),
+                float(value), *recs, ptr(visited), None, *outs)
+    elif kind == _lib.GOAL_NONE:
+        name, sizes = "mepol_rollout_mlp", (n, T, h0, h1, a_dim)
+        args = (env_id, *policy, init64, init32, *batch, *recs, ptr(visited), None)
+    elif kind == _lib.GOAL_BALL:
+        name, sizes = "mepol_rollout_goal", (env_id, n, T, h0, h1, a_dim)
+        args = (env_id, *policy, ptr(init), *batch, float(gx), float(gy), float(value), *recs,
+                *outs)
+    else:
+        name, sizes = "mepol_rollout_goal_threshold", (env_id, n, T, h0, h1, a_dim)
+        args = (env_id, *policy, init64, init32, *batch, int(coord), float(value), *recs, *outs)
+    ws = _ws_or_cached(None, init.device, "rollout", name[len("mepol_"):], *sizes)
+    return _rollout_mw(name, args, (W1, b1, W2t, b2, Wm, bm, log_std, init, noise), ws, n, T,
+                       defer_check)
+
+
+def _check_batch(who, noise, init, states_rec, actions_rec, visited, goal_out, policy_fits):
+    """The shape check of the checked rollouts: `policy_fits` is the family's own half."""
+    T, n, a_dim = noise.shape
+    fits = (policy_fits and tuple(init.shape) == (n, 2) and tuple(states_rec.shape) == (n, T + 1, 2)
+            and tuple(actions_rec.shape) == (n, T, a_dim)
+            and (visited is None or tuple(visited.shape) == (n, T, 2)))
+    if fits and goal_out is not None:
+        rewards_rec, len_out, done_out = goal_out
+        fits = tuple(rewards_rec.shape) == (n, T) and len_out.numel() == n and done_out.numel() == n
+    if not fits:
+        raise ValueError(f"{who}: tensor shapes do not fit the policy / batch")
+
+
+def _check_dtypes(who, f64, f32, states_rec, actions_rec, visited=None, goal_out=None):
+    """The dtype / contiguity check of the checked rollouts: `f64` and `f32` are the inputs of
+    each type; the records are f32 (visited f64, len / done int32) and contiguous."""
+    rewards = () if goal_out is None else goal_out[:1]
+    ints = () if goal_out is None else goal_out[1:]
+    vis = () if visited is None else (visited,)
+    if (any(t.dtype != torch.float64 for t in (*f64, *vis))
+            or any(t.dtype != torch.float32 for t in (*f32, states_rec, actions_rec, *rewards))
+            or any(t.dtype != torch.int32 for t in ints)
+            or not all(t.is_contiguous() for t in (states_rec, actions_rec, *vis, *rewards, *ints))):
+        raise ValueError(f"{who}: f64 policy / noise / visited, f32 contiguous records"
+                         if goal_out is None else
+                         f"{who}: f64 policy / noise, f32 contiguous records, int32 len / done")
+
+
+def _check_two_layer(who, W1, b1, W2, b2, Wm, bm, log_std, init, noise, states_rec, actions_rec,
+                     goal_out, f32_init):
+    """The two-layer goal rollouts' argument checks; f32_init: init must be f32 (else its dtype
+    is the caller's to check)."""
+    _require_device(init, noise, states_rec, actions_rec, *goal_out, W1, b1, W2, b2, Wm, bm,
+                    log_std)
+    a_dim, h0, h1 = noise.shape[2], W1.shape[0], W2.shape[0]
+    _check_batch(who, noise, init, states_rec, actions_rec, None, goal_out,
+                 tuple(W1.shape) == (h0, 2) and tuple(W2.shape) == (h1, h0)
+                 and tuple(Wm.shape) == (a_dim, h1))
+    _check_dtypes(who, (W1, b1, W2, b2, Wm, bm, log_std, noise), (init,) if f32_init else (),
+                  states_rec, actions_rec, goal_out=goal_out)
+
+
+def _check_deep(who, layers, Wm, bm, log_std, init, noise, states_rec, actions_rec, visited,
+                goal_out, f64_init, f32_init):
+    """The deep rollouts' argument checks; f64_init / f32_init: init must have that dtype (with
+    neither, its dtype is the caller's to check)."""
+    params = [t for p in layers for t in p]
+    a_dim = noise.shape[2]
+    fan_in = [2] + [W.shape[0] for W, _ in layers]
+    _check_batch(who, noise, init, states_rec, actions_rec, visited, goal_out,
+                 all(tuple(W.shape) == (b.numel(), f) for (W, b), f in zip(layers, fan_in))
+                 and tuple(Wm.shape) == (a_dim, fan_in[-1]) and bm.numel() == a_dim
+                 and log_std.numel() == a_dim)
+    _check_dtypes(who, params + [Wm, bm, log_std, noise] + ([init] if f64_init else []),
+                  (init,) if f32_init else (), states_rec, actions_rec, visited, goal_out)
+
+
+def _rollout_deep_packed(env_id, mz, kind, layers, Wm, bm, log_std, init, noise, states_rec,
+                         actions_rec, visited=None, goal=_NO_GOAL, goal_out=(None, None, None)):
+    """The deep rollouts behind the wrappers' own checks: W_2 .. W_L transposed and packed, then
+    the C entry point of this (env_id, goal kind) -- mepol_rollout_deep_maze with mz (env_id 2),
+    else mepol_rollout_deep, mepol_rollout_deep_goal (ball) or mepol_rollout_deep_goal_threshold.
+    goal = (x, y, coord, value), goal_out = (rewards_rec, len_out, done_out)."""
+    T, n, a_dim = noise.shape
+    (W1, b1), rest = layers[0], layers[1:]
+    widths = (ctypes.c_int * len(layers))(*[W.shape[0] for W, _ in layers])
+    Wt = torch.cat([W.t().reshape(-1) for W, _ in rest])
+    bt = torch.cat([b.reshape(-1) for _, b in rest])
+    # (contiguous copies stay referenced until the launch is queued)
+    W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
+                                                                     noise))
+    if mz is not None and init.dtype != torch.float32:
+        raise ValueError("a box maze's init is f32 [n, 2]")
+    gx, gy, coord, value = goal
+    policy = (len(layers), widths, ptr(W1), ptr(b1), ptr(Wt), ptr(bt), ptr(Wm), ptr(bm),
+              ptr(log_std), a_dim)
+    init64, init32 = (ptr(init) if env_id == e else None for e in (0, 1))
+    batch, recs = (ptr(noise), n, T), (ptr(states_rec), ptr(actions_rec))
+    outs = tuple(ptr(t) for t in goal_out)
+    if mz is not None:
+        name = "mepol_rollout_deep_maze"
+        args = (mz, kind, *policy, ptr(init), *batch, float(gx), float(gy), int(coord),
+                float(value), *recs, ptr(visited), None, *outs)
+    elif kind == _lib.GOAL_NONE:
+        name = "mepol_rollout_deep"
+        args = (env_id, *policy, init64, init32, *batch, *recs, ptr(visited), None)
+    elif kind == _lib.GOAL_BALL:
+        name = "mepol_rollout_deep_goal"
+        args = (env_id, *policy, ptr(init), *batch, float(gx), float(gy), float(value), *recs,
+                *outs)
+    else:
+        name = "mepol_rollout_deep_goal_threshold"
+        args = (env_id, *policy, init64, init32, *batch, int(coord), float(value), *recs, *outs)
+    # (the goal entry points share mepol_rollout_deep's workspace)
+    ws = _ws_or_cached(None, init.device, "rollout",
+                       "rollout_deep_maze" if mz is not None else "rollout_deep", n, T, len(layers),
+                       widths, a_dim)
+    call(name, *args, ptr(ws), ws.numel(), _stream())
 
 
 def rollout_deep(env_id, layers, Wm, bm, log_std, init, noise, states_rec, actions_rec,
@@ -961,51 +1053,24 @@ def rollout_deep(env_id, layers, Wm, bm, log_std, init, noise, states_rec, actio
     _require_device(init, noise, states_rec, actions_rec, visited, Wm, bm, log_std,
                     *[t for p in layers for t in p])
     mz = _maze_arg("rollout_deep", env_id, maze)
-    T, n, a_dim = noise.shape
-    (W1, b1), rest = layers[0], layers[1:]
-    fan_in = [2] + [W.shape[0] for W, _ in layers]
-    if (any(tuple(W.shape) != (b.numel(), f) for (W, b), f in zip(layers, fan_in))
-            or tuple(Wm.shape) != (a_dim, fan_in[-1]) or bm.numel() != a_dim
-            or log_std.numel() != a_dim or tuple(init.shape) != (n, 2)
-            or tuple(states_rec.shape) != (n, T + 1, 2) or tuple(actions_rec.shape) != (n, T, a_dim)
-            or (visited is not None and tuple(visited.shape) != (n, T, 2))):
-        raise ValueError("rollout_deep: tensor shapes do not fit the policy / batch")
-    f64 = [t for p in layers for t in p] + [Wm, bm, log_std, noise] + (
-        [visited] if visited is not None else []) + ([init] if env_id == 0 else [])
-    if (any(t.dtype != torch.float64 for t in f64) or (env_id != 0 and init.dtype != torch.float32)
-            or states_rec.dtype != torch.float32 or actions_rec.dtype != torch.float32
-            or not (states_rec.is_contiguous() and actions_rec.is_contiguous()
-                    and (visited is None or visited.is_contiguous()))):
-        raise ValueError("rollout_deep: f64 policy / noise / visited, f32 contiguous records")
-    widths = (ctypes.c_int * len(layers))(*[W.shape[0] for W, _ in layers])
-    Wt = torch.cat([W.t().reshape(-1) for W, _ in rest])
-    bt = torch.cat([b.reshape(-1) for _, b in rest])
-    # (contiguous copies stay referenced until the launch is queued)
-    W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
-                                                                     noise))
-    if mz is not None:
-        return _rollout_deep_maze(mz, _lib.GOAL_NONE, widths, W1, b1, Wt, bt, Wm, bm, log_std, init,
-                                  noise, states_rec, actions_rec, visited=visited)
-    init64 = init if env_id == 0 else None
-    init32 = init if env_id == 1 else None
-    ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
-                       a_dim)
-    call("mepol_rollout_deep", env_id, len(layers), widths, ptr(W1), ptr(b1), ptr(Wt), ptr(bt),
-         ptr(Wm), ptr(bm), ptr(log_std), a_dim, ptr(init64), ptr(init32), ptr(noise), n, T,
-         ptr(states_rec), ptr(actions_rec), ptr(visited), None, ptr(ws), ws.numel(), _stream())
+    _check_deep("rollout_deep", layers, Wm, bm, log_std, init, noise, states_rec, actions_rec,
+                visited, None, env_id == 0, env_id != 0)
+    _rollout_deep_packed(env_id, mz, _lib.GOAL_NONE, layers, Wm, bm, log_std, init, noise,
+                         states_rec, actions_rec, visited=visited)
 
 
-def _maze_plan(kind, n, h0, h1, a_dim):
+def _plan(name, *args):
+    """{"workgroups_per_traj", "k_chunks"} of a two-layer *_plan_info entry point."""
     wg, kc = ctypes.c_int(), ctypes.c_int()
-    call("mepol_rollout_maze_plan_info", kind, n, h0, h1, a_dim, ctypes.byref(wg),
-         ctypes.byref(kc))
+    call(name, *args, ctypes.byref(wg), ctypes.byref(kc))
     return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
 
 
-def _deep_maze_plan(kind, widths, a_dim):
+def _deep_plan(name, widths, a_dim, *lead):
+    """{"resident_workgroups"} of a deep *_plan_info entry point with its leading arguments."""
     wg = ctypes.c_int()
     arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
-    call("mepol_rollout_deep_maze_plan_info", kind, len(widths), arr, a_dim, ctypes.byref(wg))
+    call(name, *lead, len(widths), arr, a_dim, ctypes.byref(wg))
     return {"resident_workgroups": wg.value}
 
 
@@ -1014,31 +1079,24 @@ def rollout_mlp_plan(n, h0, h1, a_dim, env_id=None):
     the layer-2 summation order it commits to (oracle.rollout_kordered's k_chunks).  env_id 2: the
     maze instance's own answer (MountainCar and GridWorld share one)."""
     if env_id == MAZE:
-        return _maze_plan(_lib.GOAL_NONE, n, h0, h1, a_dim)
-    wg, kc = ctypes.c_int(), ctypes.c_int()
-    call("mepol_rollout_mlp_plan_info", n, h0, h1, a_dim, ctypes.byref(wg), ctypes.byref(kc))
-    return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
+        return _plan("mepol_rollout_maze_plan_info", _lib.GOAL_NONE, n, h0, h1, a_dim)
+    return _plan("mepol_rollout_mlp_plan_info", n, h0, h1, a_dim)
 
 
 def rollout_deep_plan(env_id, widths, a_dim):
     """{"resident_workgroups"}: trajectories of rollout_deep itself (the instance without a goal
     on this env) the device holds at once for hidden layers of these widths."""
     if env_id == MAZE:
-        return _deep_maze_plan(_lib.GOAL_NONE, widths, a_dim)
-    wg = ctypes.c_int()
-    arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
-    call("mepol_rollout_deep_plan_info", env_id, len(widths), arr, a_dim, ctypes.byref(wg))
-    return {"resident_workgroups": wg.value}
+        return _deep_plan("mepol_rollout_deep_maze_plan_info", widths, a_dim, _lib.GOAL_NONE)
+    return _deep_plan("mepol_rollout_deep_plan_info", widths, a_dim, env_id)
 
 
 def rollout_goal_plan(n, h0, h1, a_dim=2, env_id=1):
     """rollout_mlp_plan for rollout_goal: the form the goal-mode kernel's own occupancy gives
     (env_id 2: the maze's ball-goal instance)."""
     if env_id == MAZE:
-        return _maze_plan(_lib.GOAL_BALL, n, h0, h1, a_dim)
-    wg, kc = ctypes.c_int(), ctypes.c_int()
-    call("mepol_rollout_goal_plan_info", n, h0, h1, a_dim, ctypes.byref(wg), ctypes.byref(kc))
-    return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
+        return _plan("mepol_rollout_maze_plan_info", _lib.GOAL_BALL, n, h0, h1, a_dim)
+    return _plan("mepol_rollout_goal_plan_info", n, h0, h1, a_dim)
 
 
 def rollout_goal(W1, b1, W2, b2, Wm, bm, log_std, init, noise, goal_xy, radius, states_rec,
@@ -1054,53 +1112,15 @@ def rollout_goal(W1, b1, W2, b2, Wm, bm, log_std, init, noise, goal_xy, radius, 
     the one-workgroup form (the same bits).  defer_check=True leaves that to the caller: the
     return value is (err, rerun), a device int32 [1] view of the word and the re-run, so the word
     can be read together with the caller's own results in one synchronisation."""
-    _require_device(init, noise, states_rec, actions_rec, rewards_rec, len_out, done_out, W1, b1,
-                    W2, b2, Wm, bm, log_std)
-    T, n, a_dim = noise.shape
-    h0, h1 = W1.shape[0], W2.shape[0]
-    if (tuple(W1.shape) != (h0, 2) or tuple(W2.shape) != (h1, h0) or tuple(Wm.shape) != (a_dim, h1)
-            or tuple(init.shape) != (n, 2) or tuple(states_rec.shape) != (n, T + 1, 2)
-            or tuple(actions_rec.shape) != (n, T, a_dim) or tuple(rewards_rec.shape) != (n, T)
-            or len_out.numel() != n or done_out.numel() != n):
-        raise ValueError("rollout_goal: tensor shapes do not fit the policy / batch")
-    if (any(t.dtype != torch.float64 for t in (W1, b1, W2, b2, Wm, bm, log_std, noise))
-            or any(t.dtype != torch.float32 for t in (init, states_rec, actions_rec, rewards_rec))
-            or len_out.dtype != torch.int32 or done_out.dtype != torch.int32
-            or not all(t.is_contiguous() for t in (states_rec, actions_rec, rewards_rec, len_out,
-                                                   done_out))):
-        raise ValueError("rollout_goal: f64 policy / noise, f32 contiguous records, int32 len / done")
+    goal_out = (rewards_rec, len_out, done_out)
+    _check_two_layer("rollout_goal", W1, b1, W2, b2, Wm, bm, log_std, init, noise, states_rec,
+                     actions_rec, goal_out, True)
     W2t = W2.t().contiguous()
     mz = _maze_arg("rollout_goal", env_id, maze)
-    if mz is not None:
-        gx, gy = (float(v) for v in goal_xy)
-        return _rollout_maze(mz, _lib.GOAL_BALL, W1, b1, W2t, b2, Wm, bm, log_std, init, noise,
-                             states_rec, actions_rec, goal=(gx, gy, 0, radius),
-                             rewards_rec=rewards_rec, len_out=len_out, done_out=done_out,
-                             defer_check=defer_check)
-    # (contiguous copies stay referenced until the launch is queued)
-    W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
-                                                                          log_std, init, noise))
-    ws = _ws_or_cached(None, init.device, "rollout", "rollout_goal", env_id, n, T, h0, h1, a_dim)
     gx, gy = (float(v) for v in goal_xy)
-    args = (env_id, ptr(W1), ptr(b1), h0, ptr(W2t), ptr(b2), h1, ptr(Wm), ptr(bm), ptr(log_std),
-            a_dim, ptr(init), ptr(noise), n, T, gx, gy, float(radius), ptr(states_rec),
-            ptr(actions_rec), ptr(rewards_rec), ptr(len_out), ptr(done_out))
-    keep = (W1, b1, W2t, b2, Wm, bm, log_std, init, noise)
-    call("mepol_rollout_goal", *args, ptr(ws), ws.numel(), _stream())
-
-    def rerun(_keep=keep):
-        import warnings
-
-        warnings.warn("mepol_rollout_goal: workgroups of a trajectory were not co-resident; "
-                      "re-ran the one-workgroup form")
-        call("mepol_rollout_goal", *args, None, 0, _stream())
-
-    err = ws[:4].view(torch.int32)
-    if defer_check:
-        return err, rerun
-    if n > 0 and T > 0 and int(err[0].item()) != 0:
-        rerun()
-    return None
+    return _rollout_two_layer(env_id, mz, _lib.GOAL_BALL, W1, b1, W2t, b2, Wm, bm, log_std, init,
+                              noise, states_rec, actions_rec, goal=(gx, gy, 0, radius),
+                              goal_out=goal_out, defer_check=defer_check)
 
 
 def rollout_deep_goal_plan(widths, a_dim=2, env_id=1):
@@ -1108,11 +1128,8 @@ def rollout_deep_goal_plan(widths, a_dim=2, env_id=1):
     hidden layers of these widths (the goal-mode kernel's occupancy times the CU count; env_id 2:
     the maze's ball-goal instance)."""
     if env_id == MAZE:
-        return _deep_maze_plan(_lib.GOAL_BALL, widths, a_dim)
-    wg = ctypes.c_int()
-    arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
-    call("mepol_rollout_deep_goal_plan_info", len(widths), arr, a_dim, ctypes.byref(wg))
-    return {"resident_workgroups": wg.value}
+        return _deep_plan("mepol_rollout_deep_maze_plan_info", widths, a_dim, _lib.GOAL_BALL)
+    return _deep_plan("mepol_rollout_deep_goal_plan_info", widths, a_dim)
 
 
 def rollout_deep_goal(layers, Wm, bm, log_std, init, noise, goal_xy, radius, states_rec,
@@ -1126,53 +1143,23 @@ def rollout_deep_goal(layers, Wm, bm, log_std, init, noise, goal_xy, radius, sta
     check: the workgroups exchange nothing."""
     _require_device(init, noise, states_rec, actions_rec, rewards_rec, len_out, done_out, Wm, bm,
                     log_std, *[t for p in layers for t in p])
-    T, n, a_dim = noise.shape
-    (W1, b1), rest = layers[0], layers[1:]
-    fan_in = [2] + [W.shape[0] for W, _ in layers]
-    if (any(tuple(W.shape) != (b.numel(), f) for (W, b), f in zip(layers, fan_in))
-            or tuple(Wm.shape) != (a_dim, fan_in[-1]) or bm.numel() != a_dim
-            or log_std.numel() != a_dim or tuple(init.shape) != (n, 2)
-            or tuple(states_rec.shape) != (n, T + 1, 2) or tuple(actions_rec.shape) != (n, T, a_dim)
-            or tuple(rewards_rec.shape) != (n, T) or len_out.numel() != n
-            or done_out.numel() != n):
-        raise ValueError("rollout_deep_goal: tensor shapes do not fit the policy / batch")
-    f64 = [t for p in layers for t in p] + [Wm, bm, log_std, noise]
-    if (any(t.dtype != torch.float64 for t in f64)
-            or any(t.dtype != torch.float32 for t in (init, states_rec, actions_rec, rewards_rec))
-            or len_out.dtype != torch.int32 or done_out.dtype != torch.int32
-            or not all(t.is_contiguous() for t in (states_rec, actions_rec, rewards_rec, len_out,
-                                                   done_out))):
-        raise ValueError("rollout_deep_goal: f64 policy / noise, f32 contiguous records, int32 "
-                         "len / done")
-    widths = (ctypes.c_int * len(layers))(*[W.shape[0] for W, _ in layers])
-    Wt = torch.cat([W.t().reshape(-1) for W, _ in rest])
-    bt = torch.cat([b.reshape(-1) for _, b in rest])
-    # (contiguous copies stay referenced until the launch is queued)
-    W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
-                                                                     noise))
+    goal_out = (rewards_rec, len_out, done_out)
+    _check_deep("rollout_deep_goal", layers, Wm, bm, log_std, init, noise, states_rec, actions_rec,
+                None, goal_out, False, True)
     gx, gy = (float(v) for v in goal_xy)
     mz = _maze_arg("rollout_deep_goal", env_id, maze)
-    if mz is not None:
-        return _rollout_deep_maze(mz, _lib.GOAL_BALL, widths, W1, b1, Wt, bt, Wm, bm, log_std, init,
-                                  noise, states_rec, actions_rec, goal=(gx, gy, 0, radius),
-                                  rewards_rec=rewards_rec, len_out=len_out, done_out=done_out)
-    ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
-                       a_dim)
-    call("mepol_rollout_deep_goal", env_id, len(layers), widths, ptr(W1), ptr(b1), ptr(Wt),
-         ptr(bt), ptr(Wm), ptr(bm), ptr(log_std), a_dim, ptr(init), ptr(noise), n, T, gx, gy,
-         float(radius), ptr(states_rec), ptr(actions_rec), ptr(rewards_rec), ptr(len_out),
-         ptr(done_out), ptr(ws), ws.numel(), _stream())
+    _rollout_deep_packed(env_id, mz, _lib.GOAL_BALL, layers, Wm, bm, log_std, init, noise,
+                         states_rec, actions_rec, goal=(gx, gy, 0, radius), goal_out=goal_out)
 
 
 def _threshold_init(who, env_id, init):
     """The init tensor's dtype rule of the threshold-goal rollouts: f64 for MountainCar (env_id
-    0), f32 for GridWorld (1); returns (init64, init32) for the C ABI."""
+    0), f32 for GridWorld (1) and the box maze (2)."""
     if env_id not in (0, 1, MAZE):
         raise ValueError(f"{who}: env_id 0 (MountainCar), 1 (GridWorld) or 2 (box maze)")
     if init.dtype != (torch.float64 if env_id == 0 else torch.float32):
         raise ValueError(f"{who}: init is f64 for MountainCar (env_id 0), f32 for GridWorld (1) "
                          "and the box maze (2)")
-    return (init, None) if env_id == 0 else (None, init)
 
 
 def rollout_goal_threshold_plan(env_id, n, h0, h1, a_dim=None):
@@ -1180,11 +1167,8 @@ def rollout_goal_threshold_plan(env_id, n, h0, h1, a_dim=None):
     instance that runs (env x threshold goal) gives.  a_dim defaults to the env's."""
     a_dim = (1 if env_id == 0 else 2) if a_dim is None else a_dim
     if env_id == MAZE:
-        return _maze_plan(_lib.GOAL_THRESHOLD, n, h0, h1, a_dim)
-    wg, kc = ctypes.c_int(), ctypes.c_int()
-    call("mepol_rollout_goal_threshold_plan_info", env_id, n, h0, h1, a_dim, ctypes.byref(wg),
-         ctypes.byref(kc))
-    return {"workgroups_per_traj": wg.value, "k_chunks": kc.value}
+        return _plan("mepol_rollout_maze_plan_info", _lib.GOAL_THRESHOLD, n, h0, h1, a_dim)
+    return _plan("mepol_rollout_goal_threshold_plan_info", env_id, n, h0, h1, a_dim)
 
 
 def rollout_goal_threshold(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise, coord, threshold,
@@ -1195,54 +1179,16 @@ def rollout_goal_threshold(env_id, W1, b1, W2, b2, Wm, bm, log_std, init, noise,
     state[coord] >= threshold, compared in f64 on the env's own state (reward 1, done), or after T
     steps.  coord is 0 or 1; the threshold may be +-inf, not NaN.  Outputs, the error word,
     defer_check and the re-run of the one-workgroup form as rollout_goal."""
-    _require_device(init, noise, states_rec, actions_rec, rewards_rec, len_out, done_out, W1, b1,
-                    W2, b2, Wm, bm, log_std)
-    T, n, a_dim = noise.shape
-    h0, h1 = W1.shape[0], W2.shape[0]
-    if (tuple(W1.shape) != (h0, 2) or tuple(W2.shape) != (h1, h0) or tuple(Wm.shape) != (a_dim, h1)
-            or tuple(init.shape) != (n, 2) or tuple(states_rec.shape) != (n, T + 1, 2)
-            or tuple(actions_rec.shape) != (n, T, a_dim) or tuple(rewards_rec.shape) != (n, T)
-            or len_out.numel() != n or done_out.numel() != n):
-        raise ValueError("rollout_goal_threshold: tensor shapes do not fit the policy / batch")
-    if (any(t.dtype != torch.float64 for t in (W1, b1, W2, b2, Wm, bm, log_std, noise))
-            or any(t.dtype != torch.float32 for t in (states_rec, actions_rec, rewards_rec))
-            or len_out.dtype != torch.int32 or done_out.dtype != torch.int32
-            or not all(t.is_contiguous() for t in (states_rec, actions_rec, rewards_rec, len_out,
-                                                   done_out))):
-        raise ValueError("rollout_goal_threshold: f64 policy / noise, f32 contiguous records, "
-                         "int32 len / done")
+    goal_out = (rewards_rec, len_out, done_out)
+    _check_two_layer("rollout_goal_threshold", W1, b1, W2, b2, Wm, bm, log_std, init, noise,
+                     states_rec, actions_rec, goal_out, False)
     W2t = W2.t().contiguous()
     mz = _maze_arg("rollout_goal_threshold", env_id, maze)
-    # (contiguous copies stay referenced until the launch is queued)
-    W1, b1, b2, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, b2, Wm, bm,
-                                                                          log_std, init, noise))
-    init64, init32 = _threshold_init("rollout_goal_threshold", env_id, init)
-    if mz is not None:
-        return _rollout_maze(mz, _lib.GOAL_THRESHOLD, W1, b1, W2t, b2, Wm, bm, log_std, init, noise,
-                             states_rec, actions_rec, goal=(0.0, 0.0, coord, threshold),
-                             rewards_rec=rewards_rec, len_out=len_out, done_out=done_out,
-                             defer_check=defer_check)
-    ws = _ws_or_cached(None, init.device, "rollout", "rollout_goal_threshold", env_id, n, T, h0,
-                       h1, a_dim)
-    args = (env_id, ptr(W1), ptr(b1), h0, ptr(W2t), ptr(b2), h1, ptr(Wm), ptr(bm), ptr(log_std),
-            a_dim, ptr(init64), ptr(init32), ptr(noise), n, T, int(coord), float(threshold),
-            ptr(states_rec), ptr(actions_rec), ptr(rewards_rec), ptr(len_out), ptr(done_out))
-    keep = (W1, b1, W2t, b2, Wm, bm, log_std, init, noise)
-    call("mepol_rollout_goal_threshold", *args, ptr(ws), ws.numel(), _stream())
-
-    def rerun(_keep=keep):
-        import warnings
-
-        warnings.warn("mepol_rollout_goal_threshold: workgroups of a trajectory were not "
-                      "co-resident; re-ran the one-workgroup form")
-        call("mepol_rollout_goal_threshold", *args, None, 0, _stream())
-
-    err = ws[:4].view(torch.int32)
-    if defer_check:
-        return err, rerun
-    if n > 0 and T > 0 and int(err[0].item()) != 0:
-        rerun()
-    return None
+    _threshold_init("rollout_goal_threshold", env_id, init)
+    return _rollout_two_layer(env_id, mz, _lib.GOAL_THRESHOLD, W1, b1, W2t, b2, Wm, bm, log_std,
+                              init, noise, states_rec, actions_rec,
+                              goal=(0.0, 0.0, coord, threshold), goal_out=goal_out,
+                              defer_check=defer_check)
 
 
 def rollout_deep_goal_threshold_plan(env_id, widths, a_dim=None):
@@ -1250,12 +1196,8 @@ def rollout_deep_goal_threshold_plan(env_id, widths, a_dim=None):
     instance that runs times the CU count).  a_dim defaults to the env's."""
     a_dim = (1 if env_id == 0 else 2) if a_dim is None else a_dim
     if env_id == MAZE:
-        return _deep_maze_plan(_lib.GOAL_THRESHOLD, widths, a_dim)
-    wg = ctypes.c_int()
-    arr = (ctypes.c_int * len(widths))(*[int(w) for w in widths])
-    call("mepol_rollout_deep_goal_threshold_plan_info", env_id, len(widths), arr, a_dim,
-         ctypes.byref(wg))
-    return {"resident_workgroups": wg.value}
+        return _deep_plan("mepol_rollout_deep_maze_plan_info", widths, a_dim, _lib.GOAL_THRESHOLD)
+    return _deep_plan("mepol_rollout_deep_goal_threshold_plan_info", widths, a_dim, env_id)
 
 
 def rollout_deep_goal_threshold(env_id, layers, Wm, bm, log_std, init, noise, coord, threshold,
@@ -1266,43 +1208,14 @@ def rollout_deep_goal_threshold(env_id, layers, Wm, bm, log_std, init, noise, co
     (csrc/rollout_deep.hip, threshold instance), no error word to check."""
     _require_device(init, noise, states_rec, actions_rec, rewards_rec, len_out, done_out, Wm, bm,
                     log_std, *[t for p in layers for t in p])
-    T, n, a_dim = noise.shape
-    (W1, b1), rest = layers[0], layers[1:]
-    fan_in = [2] + [W.shape[0] for W, _ in layers]
-    if (any(tuple(W.shape) != (b.numel(), f) for (W, b), f in zip(layers, fan_in))
-            or tuple(Wm.shape) != (a_dim, fan_in[-1]) or bm.numel() != a_dim
-            or log_std.numel() != a_dim or tuple(init.shape) != (n, 2)
-            or tuple(states_rec.shape) != (n, T + 1, 2) or tuple(actions_rec.shape) != (n, T, a_dim)
-            or tuple(rewards_rec.shape) != (n, T) or len_out.numel() != n
-            or done_out.numel() != n):
-        raise ValueError("rollout_deep_goal_threshold: tensor shapes do not fit the policy / batch")
-    f64 = [t for p in layers for t in p] + [Wm, bm, log_std, noise]
-    if (any(t.dtype != torch.float64 for t in f64)
-            or any(t.dtype != torch.float32 for t in (states_rec, actions_rec, rewards_rec))
-            or len_out.dtype != torch.int32 or done_out.dtype != torch.int32
-            or not all(t.is_contiguous() for t in (states_rec, actions_rec, rewards_rec, len_out,
-                                                   done_out))):
-        raise ValueError("rollout_deep_goal_threshold: f64 policy / noise, f32 contiguous records, "
-                         "int32 len / done")
-    widths = (ctypes.c_int * len(layers))(*[W.shape[0] for W, _ in layers])
-    Wt = torch.cat([W.t().reshape(-1) for W, _ in rest])
-    bt = torch.cat([b.reshape(-1) for _, b in rest])
-    # (contiguous copies stay referenced until the launch is queued)
-    W1, b1, Wm, bm, log_std, init, noise = (t.contiguous() for t in (W1, b1, Wm, bm, log_std, init,
-                                                                     noise))
-    init64, init32 = _threshold_init("rollout_deep_goal_threshold", env_id, init)
+    goal_out = (rewards_rec, len_out, done_out)
+    _check_deep("rollout_deep_goal_threshold", layers, Wm, bm, log_std, init, noise, states_rec,
+                actions_rec, None, goal_out, False, False)
+    _threshold_init("rollout_deep_goal_threshold", env_id, init)
     mz = _maze_arg("rollout_deep_goal_threshold", env_id, maze)
-    if mz is not None:
-        return _rollout_deep_maze(mz, _lib.GOAL_THRESHOLD, widths, W1, b1, Wt, bt, Wm, bm, log_std,
-                                  init, noise, states_rec, actions_rec,
-                                  goal=(0.0, 0.0, coord, threshold), rewards_rec=rewards_rec,
-                                  len_out=len_out, done_out=done_out)
-    ws = _ws_or_cached(None, init.device, "rollout", "rollout_deep", n, T, len(layers), widths,
-                       a_dim)
-    call("mepol_rollout_deep_goal_threshold", env_id, len(layers), widths, ptr(W1), ptr(b1),
-         ptr(Wt), ptr(bt), ptr(Wm), ptr(bm), ptr(log_std), a_dim, ptr(init64), ptr(init32),
-         ptr(noise), n, T, int(coord), float(threshold), ptr(states_rec), ptr(actions_rec),
-         ptr(rewards_rec), ptr(len_out), ptr(done_out), ptr(ws), ws.numel(), _stream())
+    _rollout_deep_packed(env_id, mz, _lib.GOAL_THRESHOLD, layers, Wm, bm, log_std, init, noise,
+                         states_rec, actions_rec, goal=(0.0, 0.0, coord, threshold),
+                         goal_out=goal_out)
 
 
 def traj_budget(lens, dones, budget):

@@ -17,9 +17,7 @@
 // The fused rollout step takes the policy mean from the PyTorch MLP and Gaussian noise, forms
 // a = mean + noise * exp(log_std) (policy.py:59), records (s_t, a_t) as f32 (mepol.py:74-75,
 // 82-86) and advances the env state, all in one launch per step.
-#include "common.hpp"
-#include "env_step.hpp"
-#include "goal_mode.hpp"
+#include "rollout_core.hpp"
 
 namespace mepol {
 namespace envs {
@@ -56,7 +54,7 @@ __global__ void step_maze_kernel(float* __restrict__ s, const double* __restrict
 // One rollout step for n trajectories.  env_f64: MountainCar state [n,2] (f64);
 // env_f32: GridWorld / maze state [n,2] (f32).  policy_in [n,2] f64 receives the next policy input.
 // states_rec [n, T+1, 2] f32, actions_rec [n, T, a_dim] f32.  MZ: MazeArgs for ENV 2, else empty
-// (grid_step, env_step.hpp).
+// (EnvState::step, rollout_core.hpp).
 template <int ENV, typename... MZ>
 __global__ void rollout_step_kernel(double* __restrict__ env_f64, float* __restrict__ env_f32,
                                     const double* __restrict__ mean,
@@ -69,31 +67,17 @@ __global__ void rollout_step_kernel(double* __restrict__ env_f64, float* __restr
   if (i >= n) return;
   double act[8];
   for (int j = 0; j < a_dim && j < 8; ++j) {
-    // output = mean + randn * exp(log_std)   (policy.py:59)
-    act[j] = __dadd_rn(mean[i * a_dim + j], __dmul_rn(noise[i * a_dim + j], exp(log_std[j])));
+    act[j] = gaussian_action(mean[i * a_dim + j], noise[i * a_dim + j], exp(log_std[j]));
     actions_rec[(i * T + t) * a_dim + j] = (float)act[j];
   }
-  if constexpr (ENV == 0) {
-    double p = env_f64[2 * i], v = env_f64[2 * i + 1];
-    MountainCar::step(p, v, act[0]);
-    env_f64[2 * i] = p;
-    env_f64[2 * i + 1] = v;
-    policy_in[2 * i] = p;
-    policy_in[2 * i + 1] = v;
-    states_rec[(i * (T + 1) + t + 1) * 2 + 0] = (float)p;
-    states_rec[(i * (T + 1) + t + 1) * 2 + 1] = (float)v;
-  } else {
-    float x = env_f32[2 * i], y = env_f32[2 * i + 1];
-    grid_step<ENV>(x, y, act[0], act[1], mz...);
-    env_f32[2 * i] = x;
-    env_f32[2 * i + 1] = y;
-    policy_in[2 * i] = (double)x;
-    policy_in[2 * i + 1] = (double)y;
-    states_rec[(i * (T + 1) + t + 1) * 2 + 0] = x;
-    states_rec[(i * (T + 1) + t + 1) * 2 + 1] = y;
-  }
+  EnvState<ENV> env;
+  env.load(env_f64, env_f32, 2 * i);
+  env.step(act, mz...);
+  env.store(env_f64, env_f32, 2 * i);
+  policy_in[2 * i] = env.x0();
+  policy_in[2 * i + 1] = env.x1();
+  record_state(states_rec, i, T, t, env.x0(), env.x1());
 }
-
 
 // ---- whole rollout in one launch -----------------------------------------------------------
 // One workgroup per trajectory runs all T steps of collect_particles (mepol.py:81-90) for the
@@ -104,20 +88,12 @@ __global__ void rollout_step_kernel(double* __restrict__ env_f64, float* __restr
 // of W2^T streams from L2 each step (coalesced: one 8-byte word per thread per k).  Replaces
 // the per-step launch sequence (3 GEMMs + bias/ReLU + rollout_step, ~58 us per step even as a
 // replayed graph) with ~3 barriers per step.
-// Summation order: the layer-2 sum runs as kRollChunks fma chains over the row ranges
-// [r L, r L + L), L = ceil(h0 / kRollChunks), combined as ((c0 + c1) + c2) + c3 -- exactly the
-// multi-workgroup form's order (one chain per wave there), so both forms give the same bits
-// and the host may pick either (or fall back from one to the other) per call.
-constexpr int kRollMaxH = 512;
-// mail word not yet published (memset 0xff): a NaN bit pattern no f64 partial sum of the
-// policy's finite weights and activations produces
-constexpr unsigned long long kMailEmpty = ~0ull;
-constexpr int kRollMaxA = 8;
-constexpr int kRollChunks = 4;
-
-// Goal mode (GOAL = kGoalBall, GridWorld and the maze, or kGoalThreshold, any env): GoalArgs,
-// goal_test and goal_zero_tail of goal_mode.hpp.  MZ: MazeArgs for ENV 2, else empty (grid_step).
-template <int ENV, int U, int GOAL = kGoalNone, typename... MZ>
+// Summation order: rollout_core.hpp's, which is also the multi-workgroup form's (one layer-2
+// chain per wave there), so both forms give the same bits and the host may pick either (or fall
+// back from one to the other) per call.
+// Goal mode (GOAL = kGoalBall, GridWorld and the maze, or kGoalThreshold, any env): goal_mode.hpp.
+// MZ: MazeArgs for ENV 2, else empty (EnvState::step).
+template <int ENV, int GOAL = kGoalNone, typename... MZ>
 __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, int h0,
     const double* __restrict__ W2t, const double* __restrict__ b2, int h1,
@@ -128,6 +104,7 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     double* __restrict__ visited, double* __restrict__ final_state, int KL, GoalArgs goal,
     MZ... mz) {
   static_assert(GOAL != kGoalBall || ENV != 0, "the ball goal needs an f32-state env");
+  constexpr int U = kRollU;
   extern __shared__ double sW2[];  // [KL][blockDim.x]: W2^T rows 0 .. KL - 1
   __shared__ double sx[2];
   __shared__ int sgoal;  // GOAL: the step just taken reached the goal (thread 0 writes it)
@@ -143,22 +120,16 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
   for (int a = 0; a < kRollMaxA; ++a) wm[a] = (c1 && a < a_dim) ? Wm[a * h1 + j] : 0.0;
   for (int k = 0; k < KL; ++k) sW2[k * blockDim.x + j] = c1 ? W2t[(int64_t)k * h1 + j] : 0.0;
   const int L = (h0 + kRollChunks - 1) / kRollChunks;
-  double p = 0.0, v = 0.0;  // MountainCar state (thread 0)
-  float gx = 0.f, gy = 0.f;  // GridWorld state (thread 0)
+  // ---- the trajectory around the layers: prologue here, thread 0's serial tail and the goal exit
+  // in the step loop, the epilogue behind it.  The same text stands in rollout_deep_kernel
+  // (rollout_deep.hip); change the two together.  It is built from rollout_core.hpp's helpers but is
+  // not one itself: as helpers these pieces compiled to other, slower code.
+  EnvState<ENV> env;  // thread 0's
   if (j == 0) {
-    if (ENV == 0) {
-      p = init64[2 * i];
-      v = init64[2 * i + 1];
-      sx[0] = p;
-      sx[1] = v;
-    } else {
-      gx = init32[2 * i];
-      gy = init32[2 * i + 1];
-      sx[0] = (double)gx;
-      sx[1] = (double)gy;
-    }
-    states_rec[(i * (T + 1)) * 2 + 0] = (float)sx[0];
-    states_rec[(i * (T + 1)) * 2 + 1] = (float)sx[1];
+    env.load(init64, init32, 2 * i);
+    sx[0] = env.x0();
+    sx[1] = env.x1();
+    record_state(states_rec, i, T, -1, sx[0], sx[1]);
     if constexpr (GOAL != kGoalNone) sgoal = 0;
   }
   int64_t steps = T;  // GOAL: the episode's length
@@ -178,12 +149,10 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
     if (j == 0 && t + 1 < T)
       for (int a = 0; a < a_dim; ++a) nz_next[a] = noise[((t + 1) * n + i) * a_dim + a];
     // layer 1 (nf = 2)
-    if (c0) sh1[j] = fmax(__dadd_rn(__dadd_rn(__dmul_rn(sx[0], w1a), __dmul_rn(sx[1], w1b)), bb1),
-                          0.0);
+    if (c0) sh1[j] = layer1(sx[0], sx[1], w1a, w1b, bb1);
     __syncthreads();
-    // layer 2: h2_j = relu(sum_r c_r + b2[j]), c_r the fma chain over rows [r L, r L + L) in k
-    // order; rows below KL come from LDS, the rest stream from L2 in batches of U loads with the
-    // next batch in flight while this one is summed (L2 latency-bound: U rows per round trip)
+    // layer 2: h2_j = relu(sum_r c_r + b2[j]); the column sum is chunked_column (rollout_core.hpp)
+    // with sw_stride = blockDim.x and live = c1, written here (see there)
     double acc = 0.0;
     for (int r = 0; r < kRollChunks; ++r) {
       const int ka = min(r * L, h0), kb = min(ka + L, h0);
@@ -228,28 +197,18 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
         for (int w = 1; w < nw; ++w) mu += spart[w][a];
         mu += bm[a];
         // output = mean + randn * exp(log_std)   (policy.py:59)
-        act[a] = __dadd_rn(mu, __dmul_rn(nz[a], sd[a]));
+        act[a] = gaussian_action(mu, nz[a], sd[a]);
         actions_rec[(i * T + t) * a_dim + a] = (float)act[a];
       }
       if (t + 1 < T)
         for (int a = 0; a < a_dim; ++a) nz[a] = nz_next[a];
-      if constexpr (ENV == 0) {
-        MountainCar::step(p, v, act[0]);
-        sx[0] = p;
-        sx[1] = v;
-      } else {
-        grid_step<ENV>(gx, gy, act[0], act[1], mz...);
-        sx[0] = (double)gx;
-        sx[1] = (double)gy;
-      }
-      states_rec[(i * (T + 1) + t + 1) * 2 + 0] = (float)sx[0];
-      states_rec[(i * (T + 1) + t + 1) * 2 + 1] = (float)sx[1];
-      if (visited) {
-        visited[(i * T + t) * 2 + 0] = sx[0];
-        visited[(i * T + t) * 2 + 1] = sx[1];
-      }
+      env.step(act, mz...);
+      sx[0] = env.x0();
+      sx[1] = env.x1();
+      record_state(states_rec, i, T, t, sx[0], sx[1]);
+      record_visited(visited, i, T, t, sx[0], sx[1]);
       if constexpr (GOAL != kGoalNone) {
-        const bool hit = goal_test<GOAL, ENV>(p, v, gx, gy, goal);
+        const bool hit = env.template hit<GOAL>(goal);
         goal.rewards[i * T + t] = hit ? 1.f : 0.f;
         if (hit) sgoal = 1;
       }
@@ -262,10 +221,7 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
       }
     }
   }
-  if (j == 0 && final_state) {
-    final_state[2 * i] = sx[0];
-    final_state[2 * i + 1] = sx[1];
-  }
+  if (j == 0 && final_state) record_final(final_state, 2 * i, sx[0], sx[1]);
   if constexpr (GOAL != kGoalNone) {
     if (j == 0) {
       goal.len[i] = (int)steps;
@@ -281,8 +237,8 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
 // trajectory: workgroup p owns hidden-2 columns [64 p, 64 p + 64) and keeps their W2^T slice
 // ([h0][64] f64, <= 154 KB) in LDS for all T steps.  Per step:
 //   layer 1   all h0 columns (redundantly in every workgroup), 256 threads;
-//   layer 2   its 64 columns; wave w of the 4 sums rows k in [w L, w L + L), L = ceil(h0 / 4), as
-//             one fma chain (a single chain over 300 rows was 5.6 of the 8.4 us step:
+//   layer 2   its 64 columns; wave w of the 4 sums chunk w of rollout_core.hpp's order as one
+//             fma chain (a single chain over 300 rows was 5.6 of the 8.4 us step:
 //             tools/rollout_probe.py), and the column total is ((c0 + c1) + c2) + c3;
 //   mean      wave 0's partial of the mean layer over its 64 columns (xor shuffle tree),
 //             published as NP * a_dim self-validating 8-byte mail words (sc1 stores) and polled
@@ -295,7 +251,11 @@ __global__ __launch_bounds__(kRollMaxH) void rollout_mlp_kernel(
 // PROBE (tools/variants/rollout_probe.hip only): thread 0 of each workgroup accumulates
 // s_memtime spans of the step's phases into probe[blockIdx.x][8]; the product has PROBE = false.
 constexpr int kRollMwWaves = kRollChunks;  // one layer-2 chain per wave
-// MZ: MazeArgs for ENV 2, else empty (grid_step); every thread of every part reads the same one.
+// mail word not yet published (memset 0xff): a NaN bit pattern no f64 partial sum of the
+// policy's finite weights and activations produces
+constexpr unsigned long long kMailEmpty = ~0ull;
+// MZ: MazeArgs for ENV 2, else empty (EnvState::step); every thread of every part reads the same
+// one.
 template <int ENV, bool PROBE = false, int GOAL = kGoalNone, typename... MZ>
 __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, int h0,
@@ -339,7 +299,7 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
   // before its peers would leave them polling a word it never writes, which is a hang (bounded
   // by the spin limit: err = 1), not a wrong number.  It holds for both envs and both goal
   // kinds because every thread of every part computes the hit itself, from its own copy of the
-  // state (pp, vv) / (gx, gy), never from a flag another part wrote, and the copies are the same
+  // state (its own EnvState), never from a flag another part wrote, and the copies are the same
   // bits: each is stepped by the same instruction sequence (MountainCar::step, its cos()
   // included, or GridWorld::step) on the same action, the part-ordered sum of the same mail
   // words.  Keep the env step and the hit test free of anything that differs between parts.
@@ -377,24 +337,11 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     nz[a] = a < a_dim ? noise[i * a_dim + a] : 0.0;
   }
   // env state, stepped identically by every thread of every part of the trajectory
-  double pp = 0.0, vv = 0.0, x0, x1;
-  float gx = 0.f, gy = 0.f;
-  if (ENV == 0) {
-    pp = init64[2 * i];
-    vv = init64[2 * i + 1];
-    x0 = pp;
-    x1 = vv;
-  } else {
-    gx = init32[2 * i];
-    gy = init32[2 * i + 1];
-    x0 = (double)gx;
-    x1 = (double)gy;
-  }
+  EnvState<ENV> env;
+  env.load(init64, init32, 2 * i);
+  double x0 = env.x0(), x1 = env.x1();
   const bool rec = p == 0 && tid == 0;
-  if (rec) {
-    states_rec[(i * (T + 1)) * 2 + 0] = (float)x0;
-    states_rec[(i * (T + 1)) * 2 + 1] = (float)x1;
-  }
+  if (rec) record_state(states_rec, i, T, -1, x0, x1);
   if (tid == 0) sbad = 0;
   int64_t steps = T;  // GOAL: the episode's length
   bool hit = false;
@@ -405,13 +352,11 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
     double nz_next[kRollMaxA];
     if (t + 1 < T)
       for (int a = 0; a < a_dim; ++a) nz_next[a] = noise[((t + 1) * n + i) * a_dim + a];
-    // layer 1 (nf = 2), every column
+    // layer 1, every column
 #pragma unroll
     for (int u = 0; u < kU1; ++u) {
       const int c = tid + 64 * kRollMwWaves * u;
-      if (c < h0)
-        sh1[c] = fmax(__dadd_rn(__dadd_rn(__dmul_rn(x0, w1a[u]), __dmul_rn(x1, w1b[u])), bb1[u]),
-                      0.0);
+      if (c < h0) sh1[c] = layer1(x0, x1, w1a[u], w1b[u], bb1[u]);
     }
     __syncthreads();
     stamp(0, sh1[lane]);
@@ -468,15 +413,13 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
       for (int w = 1; w < kRollMwWaves; ++w) s += spart[w][lane];
       const double h2 = c1 ? fmax(s + bb2, 0.0) : 0.0;
       stamp(1, h2);
-      // mean layer: this part's partial over its 64 columns (xor shuffle tree), lane 0's, to
-      // this step's own mail words (pre-filled with kMailEmpty, which no partial can equal:
-      // each word validates itself, no flag)
+      // mean layer: this part's partial over its 64 columns (wave_sum), lane 0's, to this
+      // step's own mail words (pre-filled with kMailEmpty, which no partial can equal: each word
+      // validates itself, no flag)
 #pragma unroll
       for (int a = 0; a < kRollMaxA; ++a) {
         if (a < a_dim) {
-          double q = wm[a] * h2;
-#pragma unroll
-          for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m, kWave);
+          const double q = wave_sum(wm[a] * h2);
           if (lane == 0)
             __hip_atomic_store(slot + p * a_dim + a, __double_as_longlong(q), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
@@ -521,33 +464,22 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
         if (q < np) mu += wq[q];
       for (int q = np; q < nw; ++q) mu += 0.0;  // rollout_mlp_kernel's waves without columns
       mu += bmv[a];
-      // output = mean + randn * exp(log_std)   (policy.py:59)
-      act[a] = __dadd_rn(mu, __dmul_rn(nz[a], sd[a]));
+      act[a] = gaussian_action(mu, nz[a], sd[a]);
       if (rec) actions_rec[(i * T + t) * a_dim + a] = (float)act[a];
     }
     if (t + 1 < T)
       for (int a = 0; a < a_dim; ++a) nz[a] = nz_next[a];
-    if constexpr (ENV == 0) {
-      MountainCar::step(pp, vv, act[0]);
-      x0 = pp;
-      x1 = vv;
-    } else {
-      grid_step<ENV>(gx, gy, act[0], act[1], mz...);
-      x0 = (double)gx;
-      x1 = (double)gy;
-    }
+    env.step(act, mz...);
+    x0 = env.x0();
+    x1 = env.x1();
     if (rec) {
-      states_rec[(i * (T + 1) + t + 1) * 2 + 0] = (float)x0;
-      states_rec[(i * (T + 1) + t + 1) * 2 + 1] = (float)x1;
-      if (visited) {
-        visited[(i * T + t) * 2 + 0] = x0;
-        visited[(i * T + t) * 2 + 1] = x1;
-      }
+      record_state(states_rec, i, T, t, x0, x1);
+      record_visited(visited, i, T, t, x0, x1);
     }
     stamp(4, x0);
     if constexpr (GOAL != kGoalNone) {
       // the same value in every thread of every part
-      hit = goal_test<GOAL, ENV>(pp, vv, gx, gy, goal);
+      hit = env.template hit<GOAL>(goal);
       if (rec) goal.rewards[i * T + t] = hit ? 1.f : 0.f;
       if (hit) {
         steps = t + 1;
@@ -555,10 +487,7 @@ __global__ __launch_bounds__(64 * kRollMwWaves) void rollout_mlp_mw_kernel(
       }
     }
   }
-  if (rec && final_state) {
-    final_state[2 * i] = x0;
-    final_state[2 * i + 1] = x1;
-  }
+  if (rec && final_state) record_final(final_state, 2 * i, x0, x1);
   if constexpr (GOAL != kGoalNone) {
     if (rec) {
       goal.len[i] = (int)steps;
@@ -773,7 +702,7 @@ static int rollout_mlp_run(int env_id, int kind, const GoalArgs& ga, const doubl
   KL = std::max(0, std::min(KL, h0));
   const size_t lds = (size_t)KL * threads * sizeof(double);
   return rollout_instance(env_id, kind, mz, [&](auto E, auto G, const auto&... m) {
-    constexpr auto kernel = rollout_mlp_kernel<E(), 8, G(), std::decay_t<decltype(m)>...>;
+    constexpr auto kernel = rollout_mlp_kernel<E(), G(), std::decay_t<decltype(m)>...>;
     MEPOL_HIP((max_dynamic_lds<kernel>(150 * 1024)));
     hipLaunchKernelGGL(kernel, g, dim3(threads), lds, st, W1, b1, h0, W2t, b2, h1, Wm, bm, log_std,
                        a_dim, init64, init32, noise, n, T, states_rec, actions_rec, visited,

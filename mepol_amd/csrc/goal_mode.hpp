@@ -113,20 +113,7 @@ __device__ __forceinline__ bool goal_hit_threshold(double s0, double s1, const G
   return (g.coord ? s1 : s0) >= g.threshold;
 }
 
-// The hit test of a GOAL instance on ENV's state: (p, v) is MountainCar's, (gx, gy) GridWorld's
-// and the maze's.
-template <int GOAL, int ENV>
-__device__ __forceinline__ bool goal_test(double p, double v, float gx, float gy,
-                                          const GoalArgs& g) {
-  static_assert(GOAL == kGoalBall || GOAL == kGoalThreshold, "a goal kind");
-  static_assert(GOAL != kGoalBall || ENV != 0, "the ball goal needs an f32-state env");
-  if constexpr (GOAL == kGoalBall)
-    return goal_hit(gx, gy, g);
-  else if constexpr (ENV == 0)
-    return goal_hit_threshold(p, v, g);
-  else
-    return goal_hit_threshold((double)gx, (double)gy, g);
-}
+// (The hit test of a GOAL instance on ENV's own state: EnvState<ENV>::hit<GOAL>, rollout_core.hpp.)
 
 // Zeros behind an episode of `len` < T steps of trajectory i: states rows len + 1 .. T, action
 // and reward rows len .. T - 1, by all nthr threads of one workgroup.

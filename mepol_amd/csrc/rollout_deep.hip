@@ -7,42 +7,30 @@
 // k-major) of layers 2 .. L are read coalesced from L2 every step (one 8-byte word per thread
 // per k), except the leading rows of the packed W_2^T .. W_L^T buffer that fit in dynamic LDS
 // (MEPOL_ROLLOUT_KL caps their number) and stay there for all T steps.  Thread 0 forms the
-// action, steps the env and records, with the next step's noise loaded a step ahead.  Only
-// __syncthreads(): L + 1 barriers per step, no exchange between workgroups.
+// action, steps the env and records, with the next step's noise loaded a step ahead: the same
+// trajectory text as rollout_mlp_kernel's, on the helpers of rollout_core.hpp.
+// Only __syncthreads(): L + 1 barriers per step, no exchange between workgroups.
 //
-// Summation order (the contract shards and any later form rely on; the two-layer kernels
-// document the same one):
-//   layer 1       relu((x0 w0 + x1 w1) + b), explicit _rn operations;
-//   layer l >= 2  column j: four fma chains over the k ranges [r Lc, min(r Lc + Lc, h_{l-1})),
-//                 Lc = ceil(h_{l-1} / 4), each from 0.0 in k order (an empty range is 0.0),
-//                 combined as ((c0 + c1) + c2) + c3, then + b, then ReLU;
-//   mean layer    per 64-column wave the products Wm[a][j] h_L[j] summed by the xor butterfly
-//                 32, 16, .. 1 (columns past h_L are 0.0), the waves added in order, then + bm[a];
-//   action        mu + noise * exp(log_std), explicit _rn operations.
+// Summation order: rollout_core.hpp's, the contract shards and any later form rely on.
 //
-// Goal mode (GOAL = kGoalBall, GridWorld only: mepol_rollout_deep_goal; GOAL = kGoalThreshold,
-// either env: mepol_rollout_deep_goal_threshold): rollout_mlp_kernel's, with the helpers of
-// goal_mode.hpp.  Thread 0 tests the env's state after its step (goal_test), writes the reward
-// and, on a hit, sets a __shared__ flag before the step's closing barrier; behind that barrier
-// every thread reads the flag and the workgroup leaves the step loop together (no further
-// barrier), then zeroes the rows behind the episode.  Up to each episode's end the records are
-// the bits the GOAL = kGoalNone instance writes.
+// Goal mode (GOAL = kGoalBall, GridWorld and the maze: mepol_rollout_deep_goal,
+// mepol_rollout_deep_maze; GOAL = kGoalThreshold, any env: mepol_rollout_deep_goal_threshold,
+// mepol_rollout_deep_maze): rollout_mlp_kernel's, with the helpers of goal_mode.hpp.  Thread 0
+// tests the env's state after its step (EnvState::hit), writes the reward and, on a hit, sets a
+// __shared__ flag before the step's closing barrier; behind that barrier every thread reads the
+// flag and the workgroup leaves the step loop together (no further barrier), then zeroes the rows
+// behind the episode.  Up to each episode's end the records are the bits the GOAL = kGoalNone
+// instance writes.
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
 
-#include "common.hpp"
-#include "env_step.hpp"
-#include "goal_mode.hpp"
+#include "rollout_core.hpp"
 
 namespace mepol {
 namespace envs {
 
-constexpr int kDeepMaxH = 512;   // kRollMaxH of envs.hip
-constexpr int kDeepMaxA = 8;
 constexpr int kDeepMinL = 3, kDeepMaxL = 6;
-constexpr int kDeepChunks = 4;
-constexpr int kDeepU = 8;  // streamed W^T rows per batch of loads
 constexpr int kDeepLdsBytes = 150 * 1024;  // dynamic LDS for resident W^T rows (as rollout_mlp)
 
 struct DeepShape {
@@ -51,49 +39,9 @@ struct DeepShape {
   int kl[kDeepMaxL];    // kl[l], l >= 1: leading rows of layer l + 1's W^T resident in LDS
 };
 
-// Column j of one hidden layer: sum_r c_r over the kDeepChunks row ranges of W^T [hp][hl].  Rows
-// below KL come from LDS (sw, [KL][hl]), the rest stream from L2 (col = W^T + j) in batches of
-// U loads with the next batch in flight while this one is summed, as rollout_mlp_kernel does.
-// (Taking the four ranges as one stream of loads that runs ahead across the range boundaries was
-// slower, 33.6 us per step at [300, 300, 300] against 28.0 with U = 8 and 36.4 with U = 16:
-// DESIGN.md section 3, Rollout.)
-template <int U>
-__device__ __forceinline__ double deep_column(const double* __restrict__ sw,
-                                              const double* __restrict__ col,
-                                              const double* __restrict__ hin, int hp, int hl,
-                                              int KL, int j) {
-  const int Lc = (hp + kDeepChunks - 1) / kDeepChunks;
-  double acc = 0.0;
-  for (int r = 0; r < kDeepChunks; ++r) {
-    const int ka = min(r * Lc, hp), kb = min(ka + Lc, hp);
-    double c = 0.0;
-    int k = ka;
-    for (; k < min(kb, KL); ++k) c = fma(sw[k * hl + j], hin[k], c);
-    double cur[U], nxt[U];
-    const int kend = k + ((kb - k) / U) * U;
-    if (k < kend) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) cur[u] = col[(int64_t)(k + u) * hl];
-      for (; k < kend; k += U) {
-        if (k + U < kend) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) nxt[u] = col[(int64_t)(k + U + u) * hl];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) c = fma(cur[u], hin[k + u], c);
-#pragma unroll
-        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-      }
-    }
-    for (; k < kb; ++k) c = fma(col[(int64_t)k * hl], hin[k], c);
-    acc = r == 0 ? c : acc + c;
-  }
-  return acc;
-}
-
 // MZ: MazeArgs for ENV 2 (the box maze), else empty (grid_step, env_step.hpp).
 template <int ENV, int GOAL = kGoalNone, typename... MZ>
-__global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
+__global__ __launch_bounds__(kRollMaxH) void rollout_deep_kernel(
     const double* __restrict__ W1, const double* __restrict__ b1, const double* __restrict__ Wt,
     const double* __restrict__ bt, const double* __restrict__ Wm, const double* __restrict__ bm,
     const double* __restrict__ log_std, int a_dim, const double* __restrict__ init64,
@@ -105,8 +53,8 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
   extern __shared__ double sW[];  // resident rows of W_2^T .. W_L^T, layer after layer
   __shared__ double sx[2];
   __shared__ int sgoal;  // GOAL: the step just taken reached the goal (thread 0 writes it)
-  __shared__ double shid[2][kDeepMaxH];  // hidden activations, ping-pong
-  __shared__ double spart[kDeepMaxH / 64][kDeepMaxA];
+  __shared__ double shid[2][kRollMaxH];  // hidden activations, ping-pong
+  __shared__ double spart[kRollMaxH / 64][kRollMaxA];
   const int64_t i = blockIdx.x;
   const int j = threadIdx.x, lane = j & 63, wave = j >> 6;
   const int L = sh.L;
@@ -126,33 +74,27 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
   }
   const int hL = sh.h[L - 1];
   const bool cL = j < hL;
-  double wm[kDeepMaxA];
+  double wm[kRollMaxA];
 #pragma unroll
-  for (int a = 0; a < kDeepMaxA; ++a) wm[a] = (cL && a < a_dim) ? Wm[a * hL + j] : 0.0;
+  for (int a = 0; a < kRollMaxA; ++a) wm[a] = (cL && a < a_dim) ? Wm[a * hL + j] : 0.0;
   const int nwL = (hL + 63) >> 6;  // waves that hold columns of the last hidden layer
-  double p = 0.0, v = 0.0;  // MountainCar state (thread 0)
-  float gx = 0.f, gy = 0.f;  // GridWorld state (thread 0)
+  // ---- the trajectory around the layers: prologue here, thread 0's serial tail and the goal exit
+  // in the step loop, the epilogue behind it.  The same text stands in rollout_mlp_kernel
+  // (envs.hip); change the two together.  It is built from rollout_core.hpp's helpers but is
+  // not one itself: as helpers these pieces compiled to other, slower code.
+  EnvState<ENV> env;  // thread 0's
   if (j == 0) {
-    if (ENV == 0) {
-      p = init64[2 * i];
-      v = init64[2 * i + 1];
-      sx[0] = p;
-      sx[1] = v;
-    } else {
-      gx = init32[2 * i];
-      gy = init32[2 * i + 1];
-      sx[0] = (double)gx;
-      sx[1] = (double)gy;
-    }
-    states_rec[(i * (T + 1)) * 2 + 0] = (float)sx[0];
-    states_rec[(i * (T + 1)) * 2 + 1] = (float)sx[1];
+    env.load(init64, init32, 2 * i);
+    sx[0] = env.x0();
+    sx[1] = env.x1();
+    record_state(states_rec, i, T, -1, sx[0], sx[1]);
     if constexpr (GOAL != kGoalNone) sgoal = 0;
   }
   int64_t steps = T;  // GOAL: the episode's length
   // thread 0: exp(log_std) once, and the next step's noise loaded a step ahead (its global
   // latency would otherwise sit on the serial tail of every step); the load of step t + 1 is
   // consumed inside step t (nz = nz_next), so none is pending when a GOAL workgroup leaves
-  double sd[kDeepMaxA], nz[kDeepMaxA];
+  double sd[kRollMaxA], nz[kRollMaxA];
   if (j == 0) {
     for (int a = 0; a < a_dim; ++a) {
       sd[a] = exp(log_std[a]);
@@ -161,13 +103,12 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
   }
   __syncthreads();
   for (int64_t t = 0; t < T; ++t) {
-    double nz_next[kDeepMaxA];
+    double nz_next[kRollMaxA];
     if (j == 0 && t + 1 < T)
       for (int a = 0; a < a_dim; ++a) nz_next[a] = noise[((t + 1) * n + i) * a_dim + a];
     // layer 1 (nf = 2)
     if (c0)
-      shid[0][j] = fmax(
-          __dadd_rn(__dadd_rn(__dmul_rn(sx[0], w1a), __dmul_rn(sx[1], w1b)), bb1), 0.0);
+      shid[0][j] = layer1(sx[0], sx[1], w1a, w1b, bb1);
     __syncthreads();
     // layers 2 .. L: layer l + 1 reads shid[(l - 1) & 1] and writes shid[l & 1]; the last one
     // keeps its column in a register for the mean layer
@@ -180,8 +121,8 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
         hv = 0.0;
         if (j < hl) {
           const double bias = bt[boff + j];  // (an L2 hit, in flight under the column sum)
-          hv = fmax(deep_column<kDeepU>(sW + soff, Wt + woff + j, shid[(l - 1) & 1], hp, hl, kl,
-                                        j) + bias, 0.0);
+          hv = fmax(chunked_column<kRollU>(sW + soff + j, hl, Wt + woff + j, shid[(l - 1) & 1], hp,
+                                           hl, kl, true) + bias, 0.0);
         }
         if (l + 1 < L) {
           if (j < hl) shid[l & 1][j] = hv;
@@ -194,7 +135,7 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     }
     // mean layer: per-wave partial sums over its 64 columns, then waves in order
 #pragma unroll
-    for (int a = 0; a < kDeepMaxA; ++a) {
+    for (int a = 0; a < kRollMaxA; ++a) {
       if (a < a_dim) {
         double q = wm[a] * hv;
 #pragma unroll
@@ -204,34 +145,24 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
     }
     __syncthreads();
     if (j == 0) {
-      double act[kDeepMaxA];
+      double act[kRollMaxA];
       for (int a = 0; a < a_dim; ++a) {
         double mu = spart[0][a];
         for (int w = 1; w < nwL; ++w) mu += spart[w][a];
         mu += bm[a];
         // output = mean + randn * exp(log_std)   (policy.py:59)
-        act[a] = __dadd_rn(mu, __dmul_rn(nz[a], sd[a]));
+        act[a] = gaussian_action(mu, nz[a], sd[a]);
         actions_rec[(i * T + t) * a_dim + a] = (float)act[a];
       }
       if (t + 1 < T)
         for (int a = 0; a < a_dim; ++a) nz[a] = nz_next[a];
-      if constexpr (ENV == 0) {
-        MountainCar::step(p, v, act[0]);
-        sx[0] = p;
-        sx[1] = v;
-      } else {
-        grid_step<ENV>(gx, gy, act[0], act[1], mz...);
-        sx[0] = (double)gx;
-        sx[1] = (double)gy;
-      }
-      states_rec[(i * (T + 1) + t + 1) * 2 + 0] = (float)sx[0];
-      states_rec[(i * (T + 1) + t + 1) * 2 + 1] = (float)sx[1];
-      if (visited) {
-        visited[(i * T + t) * 2 + 0] = sx[0];
-        visited[(i * T + t) * 2 + 1] = sx[1];
-      }
+      env.step(act, mz...);
+      sx[0] = env.x0();
+      sx[1] = env.x1();
+      record_state(states_rec, i, T, t, sx[0], sx[1]);
+      record_visited(visited, i, T, t, sx[0], sx[1]);
       if constexpr (GOAL != kGoalNone) {
-        const bool hit = goal_test<GOAL, ENV>(p, v, gx, gy, goal);
+        const bool hit = env.template hit<GOAL>(goal);
         goal.rewards[i * T + t] = hit ? 1.f : 0.f;
         if (hit) sgoal = 1;
       }
@@ -244,10 +175,7 @@ __global__ __launch_bounds__(kDeepMaxH) void rollout_deep_kernel(
       }
     }
   }
-  if (j == 0 && final_state) {
-    final_state[2 * i] = sx[0];
-    final_state[2 * i + 1] = sx[1];
-  }
+  if (j == 0 && final_state) record_final(final_state, 2 * i, sx[0], sx[1]);
   if constexpr (GOAL != kGoalNone) {
     if (j == 0) {
       goal.len[i] = (int)steps;
@@ -262,15 +190,15 @@ constexpr size_t kDeepWorkspaceBytes = 256;  // the error-word header
 // Host-side validation shared by the two entry points; the error text names the limits.
 static bool deep_shape_ok(int env_id, int n_hidden, const int* widths, int a_dim) {
   bool ok = env_id >= 0 && env_id <= 1 && n_hidden >= kDeepMinL && n_hidden <= kDeepMaxL &&
-            widths && a_dim >= 1 && a_dim <= kDeepMaxA && !(env_id == 1 && a_dim != 2);
-  for (int l = 0; ok && l < n_hidden; ++l) ok = widths[l] >= 1 && widths[l] <= kDeepMaxH;
+            widths && a_dim >= 1 && a_dim <= kRollMaxA && !(env_id == 1 && a_dim != 2);
+  for (int l = 0; ok && l < n_hidden; ++l) ok = widths[l] >= 1 && widths[l] <= kRollMaxH;
   return ok;
 }
 
 static int deep_bad_args(const char* who) {
   set_error("%s: bad arguments (env 0 or 1, %d <= n_hidden <= %d, 1 <= width <= %d, "
             "1 <= a_dim <= %d, GridWorld a_dim = 2, no null pointers)",
-            who, kDeepMinL, kDeepMaxL, kDeepMaxH, kDeepMaxA);
+            who, kDeepMinL, kDeepMaxL, kRollMaxH, kRollMaxA);
   return kErrBadArg;
 }
 
@@ -425,7 +353,7 @@ extern "C" int mepol_rollout_deep_goal(int env_id, int n_hidden, const int* widt
       !(goal_y == goal_y) || !(radius >= 0.0)) {
     set_error("mepol_rollout_deep_goal: bad arguments (%d <= n_hidden <= %d, 1 <= width <= %d, "
               "a_dim = 2, radius >= 0, no null pointers)",
-              kDeepMinL, kDeepMaxL, kDeepMaxH);
+              kDeepMinL, kDeepMaxL, kRollMaxH);
     return kErrBadArg;
   }
   if (env_id != 1) {
@@ -451,7 +379,7 @@ extern "C" int mepol_rollout_deep_goal_plan_info(int n_hidden, const int* widths
   if (a_dim != 2 || !resident_workgroups || !deep_shape_ok(1, n_hidden, widths, a_dim)) {
     set_error("mepol_rollout_deep_goal_plan_info: bad arguments (%d <= n_hidden <= %d, "
               "1 <= width <= %d, a_dim = 2)",
-              kDeepMinL, kDeepMaxL, kDeepMaxH);
+              kDeepMinL, kDeepMaxL, kRollMaxH);
     return kErrBadArg;
   }
   return deep_resident(1, kGoalBall, n_hidden, widths, resident_workgroups);
@@ -473,7 +401,7 @@ extern "C" int mepol_rollout_deep_goal_threshold(
     set_error("mepol_rollout_deep_goal_threshold: bad arguments (env 0 with a_dim = 1 and init64 "
               "or env 1 with a_dim = 2 and init32, %d <= n_hidden <= %d, 1 <= width <= %d, coord "
               "0 or 1, threshold not NaN, no null pointers)",
-              kDeepMinL, kDeepMaxL, kDeepMaxH);
+              kDeepMinL, kDeepMaxL, kRollMaxH);
     return kErrBadArg;
   }
   if (workspace && workspace_bytes < kDeepWorkspaceBytes) {
@@ -495,7 +423,7 @@ extern "C" int mepol_rollout_deep_goal_threshold_plan_info(int env_id, int n_hid
       a_dim != (env_id == 0 ? 1 : 2)) {
     set_error("mepol_rollout_deep_goal_threshold_plan_info: bad arguments (env 0 with a_dim = 1 "
               "or env 1 with a_dim = 2, %d <= n_hidden <= %d, 1 <= width <= %d)",
-              kDeepMinL, kDeepMaxL, kDeepMaxH);
+              kDeepMinL, kDeepMaxL, kRollMaxH);
     return kErrBadArg;
   }
   return deep_resident(env_id, kGoalThreshold, n_hidden, widths, resident_workgroups);
@@ -508,7 +436,7 @@ static int deep_maze_bad_args(const char* who) {
   set_error("%s: bad arguments (goal kind 0 .. 2, %d <= n_hidden <= %d, 1 <= width <= %d, "
             "a_dim = 2; ball: radius >= 0; threshold: coord 0 or 1, threshold not NaN; no null "
             "pointers)",
-            who, kDeepMinL, kDeepMaxL, kDeepMaxH);
+            who, kDeepMinL, kDeepMaxL, kRollMaxH);
   return kErrBadArg;
 }
 

@@ -649,7 +649,22 @@ int mepol_optim_step_snapshot(int kind, int n_tensors, double* const* params,
  * W3 [1, h1], b3), updated in place; they stay on chip between steps.  scal [n_steps][2] is DEVICE
  * memory: {lr / bias_correction1, sqrt(bias_correction2)} of each step, the host-computed scalars
  * of mepol_optim_step.  loss_out [n_steps] (nullable): each step's mini-batch loss before its
- * update.  Every sum has a fixed order: the same inputs give the same bits.
+ * update.  Every sum has a fixed order: the same inputs give the same bits, and a launch of k
+ * steps followed by one of n - k steps (scal advanced) gives the bits of one launch of n.
+ * Non-finite data in a row that IS read: the ReLUs are selects, (z > 0) ? z : 0, so a NaN
+ * pre-activation is an inactive unit, not a NaN activation as in torch.  An infinite TARGET shows
+ * as it does in the loop: that step's loss_out is inf and every later one NaN, and the parameters
+ * come back NaN except what a unit that was off in that row shields (its row of W2, its b2).  A NaN
+ * or infinite STATE coordinate does NOT show in the loss: the row's h1 is 0 (NaN) or 0 / +inf per
+ * unit (inf), its value and that step's loss_out stay finite, the weight gradient puts 0 * NaN into
+ * column f of W1 (f the coordinate; for inf also into W2's columns of the units driven to +inf),
+ * and from the next step on every z1 is NaN, the first layer is off and every loss_out is finite
+ * again.  On return exactly those columns of W1 (W2) and of their moments are NaN and everything
+ * else is finite, where the loop returns a non-finite loss and every tensor NaN.  A caller that
+ * watches only the loss must therefore check the parameters too (algorithms/trpo.py's _fit_critic
+ * does, on the device: a fit with any non-finite parameter, moment or loss returns all of them
+ * NaN).  Rows that no index reads may hold anything.  eps == 0 is allowed (an element whose
+ * gradient and moments are exactly 0 then becomes NaN, as in torch).
  * 1 <= nf <= 16, 1 <= h0, h1 <= 64, 1 <= batch <= 64, n_steps >= 1, n < 2^31 (beyond:
  * MEPOL_ERR_BAD_ARG).  mepol_critic_fit_plan_info (host only, always 0): the workgroup's threads,
  * its LDS bytes, and *accepted = 1 when the shape is within those limits, else 0. */

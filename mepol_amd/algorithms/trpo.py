@@ -721,17 +721,31 @@ def _fit_critic_kernel(params, vfunc_optimizer, epoch_states, epoch_targets, cri
             state[p]["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
     g = vfunc_optimizer.param_groups[0]
     first = int(float(state[params[0]]["step"])) + 1
+    tensors = ([p.data for p in params] + [state[p]["exp_avg"] for p in params]
+               + [state[p]["exp_avg_sq"] for p in params])
     with torch.no_grad():
-        ops.critic_fit(epoch_states, epoch_targets.reshape(-1), index.to(epoch_states.device),
-                       critic_batch_size, [p.data for p in params],
-                       [state[p]["exp_avg"] for p in params],
-                       [state[p]["exp_avg_sq"] for p in params], g["lr"], betas=g["betas"],
-                       eps=g["eps"], first_step=first)
+        loss = ops.critic_fit(epoch_states, epoch_targets.reshape(-1),
+                              index.to(epoch_states.device), critic_batch_size, tensors[:6],
+                              tensors[6:12], tensors[12:], g["lr"], betas=g["betas"],
+                              eps=g["eps"], first_step=first)
+        _spread_non_finite(tensors, loss)
     for p in params:
         state[p]["step"] += n_steps
         p.grad = None
     CRITIC_FIT_STATS["kernel_calls"] += 1
     CRITIC_FIT_STATS["steps"] += n_steps
+
+
+def _spread_non_finite(tensors, loss):
+    """Make a fit that met a non-finite value show it as the host loop does.  The kernel's ReLU
+    is a select, so a NaN state coordinate leaves every loss finite and only one column of W1
+    (and of its moments) NaN, where autograd's loop returns every tensor NaN (mepol_amd.h,
+    mepol_critic_fit).  All on the device, no synchronisation: each tensor is multiplied in
+    place by 1.0 when every parameter, moment and loss is finite (the same bits) and by NaN when
+    one is not, so the next epoch's values are NaN as they would have been."""
+    flat = torch.cat([t.reshape(-1) for t in tensors] + [loss.reshape(-1)])
+    one = torch.ones((), dtype=flat.dtype, device=flat.device)
+    torch._foreach_mul_(tensors, torch.where(torch.isfinite(flat).all(), one, one * float("nan")))
 
 
 def _scalar_dtype():

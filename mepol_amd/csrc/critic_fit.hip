@@ -15,8 +15,9 @@
 //   sB1, sB2, sW3 [64], sB3           sP  per-wave partial sums of the column reductions
 // Everything is zeroed once; rows and columns past (B, h0, h1) are never written with anything
 // but zeros, so the fragments of ragged shapes are padded inside the kernel, and the code below
-// has no per-element bounds branch: a padded element's gradient, moments and parameter are 0 and
-// Adam keeps them there (0 / eps).
+// has no per-element bounds branch: a padded element's gradient and moments are 0 and stay 0, and
+// its parameter is stored as 0 whatever Adam makes of it (0 / eps; NaN when eps == 0, which would
+// reach the next step's products as 0 * NaN).
 //
 // One step, five workgroup barriers:
 //   A   rows of the step (loaded a step ago) -> sX, sT
@@ -372,13 +373,16 @@ __global__ __launch_bounds__(kThreads) void critic_fit_kernel(Args a) {
     }
     if (w < nfH1) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < 4; ++j) {
+        if (j >= nfH0) continue;  // an all-padding fragment: nW2[j] is 0 and stays 0
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          double p = sW2[sw(16 * w + frag_row(lane, q), 16 * j + fc)];
+          const int o = 16 * w + frag_row(lane, q), i = 16 * j + fc;
+          double p = sW2[sw(o, i)];
           adam_element(st, nW2[j][q], p, mW2[j][q], vW2[j][q]);
-          nW2[j][q] = p;
+          nW2[j][q] = (o < H1 && i < H0) ? p : 0.0;  // padded: 0 / eps, NaN when eps == 0
         }
+      }
     }
     __syncthreads();
 
@@ -412,10 +416,11 @@ __global__ __launch_bounds__(kThreads) void critic_fit_kernel(Args a) {
                       [&](int k, int) { return sX[k * kXS + fc]; }, ksB, acc);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        double* pp = sW1 + (16 * w + frag_row(lane, q)) * kW1S + fc;
+        const int o = 16 * w + frag_row(lane, q);
+        double* pp = sW1 + o * kW1S + fc;
         double p = *pp;
         adam_element(st, acc[0][q], p, mW1[q], vW1[q]);
-        *pp = p;
+        *pp = (o < H0 && fc < nf) ? p : 0.0;  // as for W2
       }
     }
     __syncthreads();

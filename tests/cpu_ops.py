@@ -266,6 +266,41 @@ def optim_step(kind, params, grads, exp_avg, exp_avg_sq, scalars, snapshot=None)
                 p[...] = p + (-lr) * (g / (np.sqrt(v) + eps))
 
 
+def critic_fit(states, targets, index, batch, params, exp_avg, exp_avg_sq, lr, betas=(0.9, 0.999),
+               eps=1e-8, first_step=1, loss_out=None):
+    """csrc/critic_fit.hip in plain f64 numpy, in place: numpy's own summation orders (BLAS
+    products, pairwise sums), 2 err / B as the kernel writes it, every ReLU and mask a select,
+    Adam in adam_math.hpp's op order."""
+    x_all, t_all, idx = _np(states), _np(targets), _np(index).astype(np.int64)
+    p, m, v = ([t.numpy() for t in lst] for lst in (params, exp_avg, exp_avg_sq))
+    W1, b1, W2, b2, W3, b3 = p
+    n_steps = idx.size // batch
+    loss = np.empty(n_steps)
+    w1, w2 = 1.0 - betas[0], 1.0 - betas[1]
+    with np.errstate(all="ignore"):
+        for s in range(n_steps):
+            rows = idx[s * batch:(s + 1) * batch]
+            x, t = x_all[rows], t_all[rows]
+            z1 = x @ W1.T + b1
+            h1 = _sel(z1 > 0, z1)
+            z2 = h1 @ W2.T + b2
+            h2 = _sel(z2 > 0, z2)
+            err = (h2 @ W3[0] + b3[0]) - t
+            loss[s] = np.sum(err * err) / batch
+            dv = 2.0 * err / batch
+            dz2 = _sel(z2 > 0, dv[:, None] * W3[0][None, :])
+            dz1 = _sel(z1 > 0, dz2 @ W2)
+            grads = (dz1.T @ x, dz1.sum(axis=0), dz2.T @ h1, dz2.sum(axis=0), (dv @ h2)[None, :],
+                     dv.sum()[None])
+            step = float(first_step + s)
+            step_size, bc2_sqrt = lr / (1 - betas[0] ** step), (1 - betas[1] ** step) ** 0.5
+            for pi, g, mi, vi in zip(p, grads, m, v):
+                mi[...] = mi + w1 * (g - mi)
+                vi[...] = vi * betas[1] + w2 * (g * g)
+                pi[...] = pi + (-step_size) * (mi / (np.sqrt(vi) / bc2_sqrt + eps))
+    return _into(loss_out, loss)
+
+
 # ---------------------------------------------------------------------------------------------
 # The f64 matrix-core kernels (csrc/gemm.hip, wgrad.hip, policy_fwd.hip) in plain f64 numpy.
 # Every ReLU and mask is a select, as in the kernels: a nan that is masked off (or a nan
